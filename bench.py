@@ -26,7 +26,21 @@ value_incl_gather) and done once before the root merges the slabs into the whole
 with no collective.  Barrier + synchronize bracket the timed steps; the max time over ranks is
 used.
 
-Extra fields on the JSON line:
+A plain run sets up, warms up, times `--steps` steps, writes `--dump-outputs DIR` if asked and
+prints the result line (metric, value, unit, ms_per_step, ... and the compression ratio of the
+last step).  Everything else below -- the error-bound guard, the phase and stage passes, the
+gather and the root's checks, the roofline, the other codebook modes, the host-memory path and
+the CPU baseline -- runs only with `--full`.  (The N same-field steps still run ahead of the timed
+ones, as they always have: they are part of the state `value` is measured in.  Only `--full`
+reports their rate.)
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy
+(names end in _rank<r> when N > 1): `decompressed` (the reconstructed field, f32 or f64),
+`archive` (the archive's bytes as f32) and `archive_nbytes`; an array over its share of 48 MB is
+a fixed seeded sample of its elements (sorted indices, NumPy generator, seed 0).  The inputs
+depend only on the arguments, so two builds can be compared array for array.
+
+Extra fields on the JSON line (`--full`):
   roofline      dominant kernel: algorithmic bytes / its HIP-event duration vs 8 TB/s
   cpu_baseline  the reference's own CPU path (compiled from /root/reference into
                 oracle/_ref; 1 thread, plus an all-core variant) timed on this host, N = 1 only
@@ -64,6 +78,13 @@ def parse():
                          "1 = CESM-like 3600x1800 f32; 3 = HACC-like 1-D f32 280,953,867; "
                          "4 = Nyx-like 6x512^3 f32 sharded in z-slabs over the ranks (global codebook, "
                          "gather to root); 5 = 512^3 f64 cuSZ-i spline, r2r 1e-6")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: error-bound guard, "
+                         "phase and stage passes, gather and root checks (N > 1), roofline, other codebook "
+                         "modes, host-memory path, CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs (decompressed field, archive) "
+                         "as DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--dims", default=None)
     ap.add_argument("--eb", type=float, default=None)
     ap.add_argument("--rotate", type=int, default=3,
@@ -74,10 +95,10 @@ def parse():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = an independent field per rank (the default: the path partitions, no "
                          "collective in the timed steps); strong = one field in z-slabs with a shared codebook")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-memory (PCIe) path timing")
-    ap.add_argument("--profile-only", action="store_true", help="few steps, no baselines (rocprof)")
-    ap.add_argument("--no-other-modes", action="store_true", help="skip the other codebook modes' timings")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the host-memory (PCIe) path timing")
+    ap.add_argument("--profile-only", action="store_true", help="--full: no baselines (rocprof)")
+    ap.add_argument("--no-other-modes", action="store_true", help="--full: skip the other codebook modes' timings")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="N > 1 process group: nccl (= RCCL over xGMI); gloo is a diagnostic to rehearse the "
                          "multi-rank path with several ranks on ONE GPU (collectives staged through host memory)")
@@ -192,6 +213,33 @@ def archive_view(ptr, nbytes, dev, scratch):
     return scratch[:nbytes], scratch
 
 
+DUMP_BUDGET = 48 << 20  # bytes of .npy per run, shared evenly by the ranks and the arrays
+
+
+def sample_for_dump(t, max_elems):
+    """`t` (1-D device tensor) whole, or its elements at max_elems fixed seeded indices (sorted)."""
+    import numpy as np
+    import torch
+
+    if t.numel() > max_elems:
+        idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), max_elems))
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(dirpath, world, rank, arrays):
+    """arrays: {name: 1-D device tensor}; written as float32 (float64 stays float64)."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_BUDGET // (world * len(arrays))
+    for name, t in arrays.items():
+        wide = t.dtype.is_floating_point and t.element_size() == 8
+        a = sample_for_dump(t, share // (8 if wide else 4))
+        a = a.astype(np.float64 if wide or a.dtype == np.int64 else np.float32)
+        np.save(os.path.join(dirpath, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def bench_field(args, world, rank, dist, dev):
     import numpy as np
     import torch
@@ -243,7 +291,37 @@ def bench_field(args, world, rank, dist, dev):
     mm = torch.empty(2, dtype=torch.float64, device=dev)
     nbytes_in = esz * n  # this rank's bytes
     total_bytes = esz * n_full * (world if weak else 1)
-    state = {"scratch": None, "parts": None}
+    state = {"scratch": None, "parts": None, "last": None}
+
+    def base_line(dt, nb):
+        """The result line of a plain run (`--full` adds to it); nb: this rank's last archive."""
+        return {
+            "metric": METRICS[args.config],
+            # only config 2 is BASELINE.json's metric workload; the others use the same fields
+            "value": round(total_bytes * args.steps / dt / 1e9, 2),
+            "unit": "GB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(1e3 * dt / args.steps, 4),
+            "higher_is_better": True,
+            "scaling": "strong" if sharded or (world == 1 and args.scaling == "strong") else "weak",
+            "vs_baseline": None,
+            "dtype": "f64" if esz == 8 else "f32",
+            "full": bool(args.full),
+            "data": f"synthetic (SURVEY.md §8d config-{args.config} recipe" + (", seed per rank)" if weak else ")"),
+            "config": {"workload": f"config{args.config}: {dims[0]}x{dims[1]}x{dims[2]} "
+                                   f"{'f64' if esz == 8 else 'f32'}, {'rel' if mode == cz.Rel else 'abs'} "
+                                   f"eb={args.eb}, {'spline3' if predictor == cz.Spline else 'Lorenzo'} + "
+                                   "histogram + Huffman, compress+decompress per step",
+                       "field_bytes": esz * n_full, "per_rank_bytes": nbytes_in,
+                       "parallelism": (f"dp{world} (tile-aligned z-slabs of one field: histogram all-reduce; "
+                                       "archive gather to rank 0 outside the timed steps)") if sharded else
+                                      (f"dp{world} (an independent field per rank, no collective in the timed "
+                                       "steps; archives gathered to rank 0 outside them)" if weak else "single GPU")},
+            "rotating_inputs": len(inputs),
+            "compression_ratio": round(nbytes_in / nb, 3),  # this rank's last archive
+        }
 
     def compress():
         x = inputs[cur["i"]]
@@ -293,15 +371,17 @@ def bench_field(args, world, rank, dist, dev):
     for w in range(max(args.warmup, len(inputs))):
         x = inputs[cur["i"]]
         step()
-        torch.cuda.synchronize()
-        # correctness guard on the measured configuration (error bound, every element, every field)
-        err = max(err, (d_out.double() - x.double()).abs().max().item())
+        if args.full:
+            torch.cuda.synchronize()
+            # correctness guard on the measured configuration (error bound, every element, every field)
+            err = max(err, (d_out.double() - x.double()).abs().max().item())
     cur["i"] = 0
-    eb_abs = r.header.rc.eb  # Rel mode: eb * value range
-    # the reconstruction is computed in T (lrz_x.cuhip.inl / spline3.inl), so T's rounding at the
-    # field's magnitude adds to the bound (f32 at |x| ~ 256, HACC-like config 3: ~8e-6)
-    ulp = (2.0 ** -23 if esz == 4 else 2.0 ** -52) * max(x.abs().max().item() for x in inputs)
-    assert err <= 1.001 * eb_abs + ulp, f"error bound violated: {err} > {eb_abs} (+ulp {ulp})"
+    if args.full:
+        eb_abs = r.header.rc.eb  # Rel mode: eb * value range
+        # the reconstruction is computed in T (lrz_x.cuhip.inl / spline3.inl), so T's rounding at the
+        # field's magnitude adds to the bound (f32 at |x| ~ 256, HACC-like config 3: ~8e-6)
+        ulp = (2.0 ** -23 if esz == 4 else 2.0 ** -52) * max(x.abs().max().item() for x in inputs)
+        assert err <= 1.001 * eb_abs + ulp, f"error bound violated: {err} > {eb_abs} (+ulp {ulp})"
 
     # timed region: the library's HIP-event stage timing is OFF (its event records would add
     # barrier packets to the stream); the per-stage/kernel durations come from a second pass.
@@ -313,13 +393,31 @@ def bench_field(args, world, rank, dist, dev):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step(rot=rot)
+            state["last"] = step(rot=rot)
         torch.cuda.synchronize()
         barrier()
         return time.perf_counter() - t0
 
+    # (a plain run keeps this pass although it does not report it: `value` has always been timed
+    # behind these N steps, and timed straight after the few warm-up steps it reads 3-5 % lower)
     dt_same = timed(False)  # every step on the same field (its input may stay cached)
     dt = timed(True)        # `value`: the steps cycle through the distinct fields
+    if args.dump_outputs:
+        ptr, nb = state["last"]  # the last timed step's archive; d_out holds its reconstruction
+        arch, _ = archive_view(ptr, nb, dev, None)
+        dump_outputs(args.dump_outputs, world, rank,
+                     {"decompressed": d_out, "archive": arch,
+                      "archive_nbytes": torch.tensor([nb], dtype=torch.int64, device=dev)})
+        del arch
+    if not args.full:
+        if dist is not None:
+            t = torch.tensor([dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = t.item()
+        if rank == 0:
+            print(json.dumps(base_line(dt, state["last"][1])), flush=True)
+        r.close()
+        return
     # host-clock phase split (a separate pass: each step starts and ends with an idle stream)
     acc = [0.0, 0.0, 0.0]
     for _ in range(args.steps):
@@ -342,7 +440,6 @@ def bench_field(args, world, rank, dist, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, dt_same, acc[0], acc[1], acc[2] = t.tolist()
     ms_per_step = 1e3 * dt / args.steps
-    value = total_bytes * args.steps / dt / 1e9
     st = stage_acc / args.steps
     comp_ms, decomp_ms = st[cz.T_COMPRESS], st[cz.T_DECOMPRESS]
 
@@ -515,34 +612,12 @@ def bench_field(args, world, rank, dist, dev):
         tg_ms = 1e3 * acc[1] / args.steps
         tc_ms = 1e3 * acc[0] / args.steps
         td_ms = 1e3 * acc[2] / args.steps
-        line = {
-            "metric": METRICS[args.config],
-            # only config 2 is BASELINE.json's metric workload; the others use the same fields
-            "value": round(value, 2),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if sharded or (world == 1 and args.scaling == "strong") else "weak",
-            "vs_baseline": None,
-            "dtype": "f64" if esz == 8 else "f32",
-            "data": f"synthetic (SURVEY.md §8d config-{args.config} recipe" + (", seed per rank)" if weak else ")"),
-            "config": {"workload": f"config{args.config}: {dims[0]}x{dims[1]}x{dims[2]} "
-                                   f"{'f64' if esz == 8 else 'f32'}, {'rel' if mode == cz.Rel else 'abs'} "
-                                   f"eb={args.eb}, {'spline3' if predictor == cz.Spline else 'Lorenzo'} + "
-                                   "histogram + Huffman, compress+decompress per step",
-                       "field_bytes": esz * n_full, "per_rank_bytes": nbytes_in,
-                       "parallelism": (f"dp{world} (tile-aligned z-slabs of one field: histogram all-reduce; "
-                                       "archive gather to rank 0 outside the timed steps)") if sharded else
-                                      (f"dp{world} (an independent field per rank, no collective in the timed "
-                                       "steps; archives gathered to rank 0 outside them)" if weak else "single GPU")},
+        line = base_line(dt, nb)
+        line.update({
             "compress_gbps": round(nbytes_in / (comp_ms * 1e-3) / 1e9, 2) if comp_ms > 0 else None,
             "decompress_gbps": round(nbytes_in / (decomp_ms * 1e-3) / 1e9, 2) if decomp_ms > 0 else None,
             "compress_roofline_frac": round(nbytes_in / (comp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if comp_ms > 0 else None,
             "decompress_roofline_frac": round(nbytes_in / (decomp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if decomp_ms > 0 else None,
-            "rotating_inputs": len(inputs),
             "same_field_value": round(total_bytes * args.steps / dt_same / 1e9, 2),
             "same_field_ms_per_step": round(1e3 * dt_same / args.steps, 4),
             # host clock, a separate pass in which every step starts and ends on an idle stream
@@ -573,7 +648,7 @@ def bench_field(args, world, rank, dist, dev):
             "value_exact_codebook": (other_modes or {}).get("exact", {}).get("value"),
             "other_codebook_modes": other_modes,
             "max_abs_err": err,
-        }
+        })
         if sharded:
             line["merged_archive_bytes"] = arch_bytes_total
             line["merged_decompress_ok"] = merged_ok
@@ -687,8 +762,11 @@ def bench_sharded(args, world, rank, dist, dev):
         if dist is not None:
             dist.barrier()
 
+    # a plain run times the sharded compress alone; --full: the gather beside it and the root's checks
     for _ in range(args.warmup):
-        gather(compress())
+        arch = compress()
+        if args.full:
+            gather(arch)
     torch.cuda.synchronize(dev)
     barrier()
     tc = tg = 0.0
@@ -696,12 +774,24 @@ def bench_sharded(args, world, rank, dist, dev):
         t0 = time.perf_counter()
         arch = compress()  # host-synchronous (every slab's header is read back)
         t1 = time.perf_counter()
-        got = gather(arch)
+        if args.full:
+            got = gather(arch)
         torch.cuda.synchronize(dev)
         t2 = time.perf_counter()
         tc += t1 - t0
         tg += t2 - t1
     barrier()
+    if args.dump_outputs:  # the last step's six archives (this rank's slabs), back to back
+        sizes = [nb for _, nb in arch]
+        buf = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+        off = 0
+        for p, nb in arch:
+            cz.hip_memcpy(buf.data_ptr() + off, p, nb, 3)
+            off += nb
+        torch.cuda.synchronize(dev)
+        dump_outputs(args.dump_outputs, world, rank,
+                     {"archives": buf, "archive_nbytes": torch.tensor(sizes, dtype=torch.int64, device=dev)})
+        del buf
     if dist is not None:
         t = torch.tensor([tc, tc + tg], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -712,9 +802,9 @@ def bench_sharded(args, world, rank, dist, dev):
     # elements outliers at abs 1e-4) and decompress the merged archives
     merged_ok, merged_len = None, None
     if rank == 0:
-        bufs, metas = got
+        bufs, metas = got if args.full else ([], [])
         oks = []
-        for fi in (0, 1):
+        for fi in (0, 1) if args.full else ():
             parts = []
             for b, m in zip(bufs, metas):
                 sizes = m.view(torch.int64).tolist()
@@ -740,15 +830,17 @@ def bench_sharded(args, world, rank, dist, dev):
             "metric": METRICS[4], "value": round(total_bytes * args.steps / tc / 1e9, 2), "unit": "GB/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * tc / args.steps, 4), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic (SURVEY.md §8d config-4 recipe)",
+            "vs_baseline": None, "dtype": "f32", "full": bool(args.full),
+            "data": "synthetic (SURVEY.md §8d config-4 recipe)",
             "config": {"workload": f"config4: 6 Nyx-like 512x512x512 f32 fields, {'rel' if args.rel else 'abs'} eb={eb}, z-slabs "
                                    f"{sl.dims[2]} planes per rank, global codebook per field",
                        "parallelism": f"dp{world} (z-slabs, 2 all-reduces + gather to root)"},
-            "compress_gather_ms_per_step": round(1e3 * tcg / args.steps, 4),
-            "compress_gather_gbps": round(total_bytes * args.steps / tcg / 1e9, 2),
-            "merged_field0_bytes": merged_len, "merged_fields01_decompress_ok": merged_ok,
             "archive_bytes_per_step": int(sum(nb for _, nb in arch)),
         }
+        if args.full:
+            line.update({"compress_gather_ms_per_step": round(1e3 * tcg / args.steps, 4),
+                         "compress_gather_gbps": round(total_bytes * args.steps / tcg / 1e9, 2),
+                         "merged_field0_bytes": merged_len, "merged_fields01_decompress_ok": merged_ok})
         print(json.dumps(line), flush=True)
     for r in res:
         r.close()

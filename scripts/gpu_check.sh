@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 exec scripts/gpu_job.sh \
   "tests:600:python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -p no:cacheprovider" \
-  "bench:300:python bench.py --gpus 1 --steps 20 --warmup 5" \
+  "bench:300:python bench.py --full --gpus 1 --steps 20 --warmup 5" \
   "brick:120:python scripts/brick_bench.py --reps 20" \
   "bprof:120:python scripts/brick_profile.py" \
   "stats:300:rocprofv3 --kernel-trace --stats -d gpurun_out/prof_stats -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --profile-only"

@@ -5,7 +5,9 @@
 # Usage: scripts/pmc_config.sh <tag> <config> [bench args...]
 tag=$1; cfg=$2; shift 2
 export TMPDIR=/tmp
-d=gpurun_out/pmc_$tag
+OUT=${OUT:-build/out}  # where the logs and result lines go
+mkdir -p "$OUT"
+d=$OUT/pmc_$tag
 mkdir -p $d
 B="python3 bench.py --config $cfg --steps 5 --warmup 2 --profile-only --no-e2e $@"
 timeout -k 10 180 rocprofv3 --kernel-trace --stats -d $d/stats -o run --output-format csv -- $B > $d/stats.log 2>&1 || exit 1
@@ -19,6 +21,6 @@ for x in stats fetch write; do
   f=$(find $d/$x -name "run_*.csv" | head -1); dd=$(dirname "$f"); [ "$dd" != "$d/$x" ] && cp $dd/run_*.csv $d/$x/
 done
 python3 scripts/prof_summary.py $tag $d/stats $d/fetch $d/write > $d/summary.txt && cp profiles/${tag}_summary.json profiles/pmc_config$cfg.json && cat $d/summary.txt
-mkdir -p gpurun_out/profiles_out && cp profiles/${tag}_* profiles/pmc_config$cfg.json gpurun_out/profiles_out/
-# the raw traces stay on the box (gpurun_out is copied back only under 64 MiB)
-cp $d/summary.txt gpurun_out/profiles_out/${tag}_summary.txt && rm -rf $d
+mkdir -p $OUT/profiles_out && cp profiles/${tag}_* profiles/pmc_config$cfg.json $OUT/profiles_out/
+# the raw traces stay on the box (only the summaries are kept)
+cp $d/summary.txt $OUT/profiles_out/${tag}_summary.txt && rm -rf $d

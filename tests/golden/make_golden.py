@@ -18,6 +18,8 @@ Fixtures written (data only -- inputs and expected outputs):
 * ref_codebook.npz  -- histograms and the compiled reference's canonical codebook
                        (codec/hf/src/hf_bk.seq.cc:72-145) for each: book u32[1024], revbook.
 * ref_hist.npz      -- codes and the reference serial histogram (hist_generic.seq.cc:17-30).
+* ref_ragged.npz    -- the compiled reference CPU Lorenzo-3D, plain and ZigZag, on a ragged
+                       40x24x17 integer field at eb=0.5 where most points are outliers.
 """
 import os
 import re
@@ -118,6 +120,15 @@ def main():
     codes, ov, oi = pyoracle.ref_lorenzo3d_f64(walk64, dims, 0.5)
     np.savez_compressed(os.path.join(HERE, "ref_lrz3d_f64.npz"), data=walk64, dims=np.array(dims),
                         codes=codes, ol_val=ov, ol_idx=oi)
+    # ragged field (partial tiles on every axis) where almost every point is an outlier: the
+    # reference's outputs as it wrote them (the outlier list runs past the field's end)
+    rdims = (40, 24, 17)
+    rdata = np.random.default_rng(11).integers(-4000, 4000, size=rdims[::-1]).astype(np.float32).ravel()
+    out = {"data": rdata, "dims": np.array(rdims)}
+    for tag, fn in (("", pyoracle.ref_lorenzo_c_f32), ("zz_", pyoracle.ref_lorenzo_c_zz_f32)):
+        codes, ov, oi = fn(rdata, rdims, 0.5)
+        out.update({tag + "codes": codes, tag + "ol_val": ov, tag + "ol_idx": oi})
+    np.savez_compressed(os.path.join(HERE, "ref_ragged.npz"), **out)
     print("fixtures written to", HERE)
 
 

@@ -52,7 +52,7 @@ def test_header_layout_matches_reference():
     assert C.sizeof(cz.psz_rc2) == 24 and C.sizeof(cz.psz_interp_params) == 40
 
 
-def test_c_header_compiles_and_matches():
+def test_c_header_compiles_and_matches(tmp_path):
     """Compile a C program against include/ and check sizeof/offsetof like the reference."""
     src = r'''
 #include <stddef.h>
@@ -66,7 +66,7 @@ int main(void) {
          offsetof(phf_header, entry));
   return 0;
 }'''
-    tmp = "/tmp/cusz_amd_abi_check"
+    tmp = str(tmp_path / "abi_check")
     with open(tmp + ".c", "w") as f:
         f.write(src)
     subprocess.run(["gcc", "-std=c11", "-I" + os.path.join(ROOT, "include"), "-o", tmp, tmp + ".c"], check=True)
