@@ -78,6 +78,12 @@ class psz_amd_internals(C.Structure):
                 ("layout", C.c_int), ("brick_width", C.c_int)]
 
 
+class psz_amd_region_info(C.Structure):
+    """What a region decode touches (include/cusz_amd.h psz_amd_region_info)."""
+    _fields_ = [("path", C.c_int), ("brick_lo", psz_len), ("brick_n", psz_len), ("bricks", C.c_size_t),
+                ("chunks", C.c_size_t), ("elems", C.c_size_t)]
+
+
 assert C.sizeof(psz_header) == 176, C.sizeof(psz_header)
 
 # every symbol declared in include/*.h that the library defines
@@ -110,6 +116,8 @@ EXPORTS = [
     "psz_amd_version", "psz_amd_last_create_status", "psz_amd_build_book_device",
     "psz_amd_compress_scan_float", "psz_amd_compress_scan_double", "psz_amd_compress_finish",
     "psz_amd_merge_archives", "psz_amd_value_range",
+    "psz_amd_region_plan", "psz_amd_decompress_region_float", "psz_amd_decompress_region_double",
+    "psz_amd_last_region",
 ]
 
 
@@ -175,6 +183,13 @@ def lib():
     L.psz_amd_build_book_device.restype = C.c_int
     L.psz_amd_build_book_device.argtypes = [P, C.c_int, C.c_uint32, P, P, P]
     L.psz_amd_last_create_status.restype = C.c_int
+    L.psz_amd_region_plan.restype = C.c_int
+    L.psz_amd_region_plan.argtypes = [C.POINTER(psz_header), psz_len, psz_len, C.POINTER(psz_amd_region_info)]
+    for fn in (L.psz_amd_decompress_region_float, L.psz_amd_decompress_region_double):
+        fn.restype = C.c_int
+        fn.argtypes = [P, P, C.c_size_t, psz_len, psz_len, P]
+    L.psz_amd_last_region.restype = C.c_int
+    L.psz_amd_last_region.argtypes = [P, C.POINTER(psz_amd_region_info)]
     L.phf_coarse_tune.argtypes = [C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.pszheader_filesize.restype = C.c_size_t
     L.pszheader_filesize.argtypes = [C.POINTER(psz_header)]
@@ -187,6 +202,27 @@ DECODER_AUTO, DECODER_LANE, DECODER_WAVE = 0, 1, 2
 # archive layout (PSZ_AMD_LAYOUT_*)
 LAYOUT_BRICK, LAYOUT_REFERENCE, LAYOUT_BRICK_FORCE = 0, 1, 2
 CODEBOOK_EXACT, CODEBOOK_SAMPLED, CODEBOOK_STREAM = 0, 1, 2  # PSZ_AMD_CODEBOOK_*
+REGION_FUSED, REGION_FALLBACK = 0, 1  # PSZ_AMD_REGION_*
+
+
+def _len3(v) -> psz_len:
+    x, y, z = (tuple(int(c) for c in v) + (1, 1, 1))[:3]
+    return psz_len(x, y, z)
+
+
+def _origin3(v) -> psz_len:
+    x, y, z = (tuple(int(c) for c in v) + (0, 0, 0))[:3]
+    return psz_len(x, y, z)
+
+
+def region_plan(header: psz_header, origin, extent) -> psz_amd_region_info:
+    """psz_amd_region_plan: host only; the path and the covering bricks of a box (origin, extent in
+    elements, x first) of an archive with this header.  PszError for a box outside the field."""
+    o = psz_amd_region_info()
+    st = lib().psz_amd_region_plan(C.byref(header), _origin3(origin), _len3(extent), C.byref(o))
+    if st != PSZ_SUCCESS:
+        raise PszError(st, "psz_amd_region_plan")
+    return o
 
 
 class PszError(RuntimeError):
@@ -270,6 +306,23 @@ class Resource:
         st = f(self._h, C.c_void_p(d_archive), nbytes, C.c_void_p(d_out))
         if st != PSZ_SUCCESS:
             raise PszError(st, "psz_decompress")
+
+    def decompress_region(self, d_archive: int, nbytes: int, origin, extent, d_out: int):
+        """The box of `extent` elements at `origin` (x first; missing axes: origin 0, extent 1) of
+        the archive -> d_out, a compact device array of the box (psz_amd_decompress_region_*)."""
+        L = lib()
+        f = L.psz_amd_decompress_region_float if self.dtype == F4 else L.psz_amd_decompress_region_double
+        st = f(self._h, C.c_void_p(d_archive), nbytes, _origin3(origin), _len3(extent), C.c_void_p(d_out))
+        if st != PSZ_SUCCESS:
+            raise PszError(st, "psz_amd_decompress_region")
+
+    def last_region(self) -> psz_amd_region_info:
+        """What the last region call did (the path taken after the device-side checks)."""
+        o = psz_amd_region_info()
+        st = lib().psz_amd_last_region(self._h, C.byref(o))
+        if st != PSZ_SUCCESS:
+            raise PszError(st, "psz_amd_last_region")
+        return o
 
     def set_header(self, h: psz_header):
         lib().psz_modify_resource_manager_from_header(self._h, C.byref(h))

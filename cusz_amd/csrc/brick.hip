@@ -1200,11 +1200,21 @@ __device__ __forceinline__ uint32_t col_rank(uint64_t m, uint32_t l)
 // (sequential); x then z Hillis-Steele; times 2 eb.  Outlier values (code 0) come from the ranked
 // cells (CELLS) or from `out`, where the scatter pass has put them.  Stores address the block's
 // row (y, z) as a buffer at base + y lx with z plane as the scalar offset.
-template <typename T, bool ZZ, bool BUF, int TP, bool CELLS>
+// REGION (k_brick3_region): `out` is a compact box, not the field.  The sums run as for the whole
+// block (rows 0 .. nyv - 1, planes 0 .. nzv - 1, which the caller has clipped to the box's far
+// faces); only the elements inside the box are stored, each by a guarded global store at its
+// index in the box -- no address before or past the box is ever formed.
+struct RegionClip {
+  uint32_t x0, y0, z0;  // field coordinates of the block's first element
+  uint32_t ox, oy, oz;  // box origin
+  uint32_t ex, ey, ez;  // box extent
+};
+template <typename T, bool ZZ, bool BUF, int TP, bool CELLS, bool REGION = false>
 __device__ __forceinline__ void recon_block(const uint16_t* tile, T* out, size_t plane, uint32_t lx, uint32_t nyv,
                                             uint32_t nzv, size_t base_elem, T r, T ebx2, int lane,
-                                            const BrickCells* bc = nullptr)
+                                            const BrickCells* bc = nullptr, const RegionClip* rc = nullptr)
 {
+  static_assert(!REGION || (CELLS && !BUF && !ZZ), "the region decoder reads ranked cells only");
   T* base = out + base_elem;  // element (x0, y0, z0) of this block
   const uint32_t col = rcol((uint32_t)lane);
   const uint32_t voff = col * (uint32_t)sizeof(T);
@@ -1289,6 +1299,19 @@ __device__ __forceinline__ void recon_block(const uint16_t* tile, T* out, size_t
         for (int z = 7; z >= d; z--) t[z] = t[z] + t[z - d];
 #pragma unroll
       for (int z = 0; z < 8; z++) t[z] = t[z] * ebx2;
+    }
+    if constexpr (REGION) {
+      // unsigned differences: a coordinate before the origin wraps past the extent
+      const uint32_t bx = rc->x0 + col - rc->ox, by = rc->y0 + (uint32_t)y - rc->oy;
+      if (bx < rc->ex && by < rc->ey) {
+#pragma unroll
+        for (int z = 0; z < 8; z++) {
+          const uint32_t bz = rc->z0 + (uint32_t)z - rc->oz;
+          // (32-bit index: the box is part of a field of fewer than 2^32 elements)
+          if ((uint32_t)z < nzv && bz < rc->ez) out[(size_t)((bz * rc->ey + by) * rc->ex + bx)] = t[z];
+        }
+      }
+      continue;
     }
     T* rowb = base + (size_t)y * lx;
     if constexpr (BUF) {
@@ -2028,6 +2051,128 @@ k_brick3_decode(const uint32_t* __restrict__ bitstream, uint32_t bs_words, const
   if (lane == 0)
     for (int i = 0; i < 16; i++) atomicAdd(&g_brick_prof[i], pc[i]);
 #endif
+}
+
+// ---- 3-D: region decode ---------------------------------------------------------------------
+// k_brick3_decode over the bricks that cover a box of the field, writing only the box, compactly
+// (x fastest), to `out`.  A brick is decoded whole -- its 64 rows are one wave's 64 chunks, the y
+// sums and the z scan need the rows before the box -- but no brick outside the covering box
+// bn = (bnx, bny, bnz) at brick lo = (blx, bly, blz) is fetched: work item i is brick
+// (blx + i % bnx, bly + i / bnx % bny, blz + i / (bnx bny)); par_nbit, par_entry and ol.bstart keep
+// the field's indexing.  64-column blocks only (a region is a few bricks per wave at most: one
+// brick's latency bounds it).  x: the chunk is read front to back, so the blocks left of the box
+// are decoded (and reconstructed without stores when the brick has outlier cells: the rows'
+// consumed-cell counts carry on), the blocks right of it are not.  The cells are ranked (the host
+// has read the bounds pass's verdict), non-ZigZag.  Work items are wave-major over the grid
+// (wave w of workgroup g starts at w grid + g): one brick per CU before any CU gets a second.
+template <typename T>
+__global__ void __launch_bounds__(64 * Dec3Cfg<64>::kWaves)
+k_brick3_region(const uint32_t* __restrict__ bitstream, uint32_t bs_words, const uint8_t* __restrict__ revbook,
+                int bklen, const uint32_t* __restrict__ par_nbit, const uint32_t* __restrict__ par_entry, T* out,
+                uint32_t lx, uint32_t ly, uint32_t lz, T ebx2, T r, uint32_t nbx, uint32_t nby, BrickOutliers ol,
+                RegionBox box)
+{
+  __shared__ hfd::Tab4 tb;
+  extern __shared__ __attribute__((aligned(16))) uint8_t dsm[];
+  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  typedef Dec3Cfg<64> C;
+  constexpr int BLK = 64;
+  uint8_t* wbase = dsm + (size_t)wid * C::kWaveBytes;
+  uint16_t* tile = reinterpret_cast<uint16_t*>(wbase + kD4Tile);
+  uint32_t* cval = reinterpret_cast<uint32_t*>(wbase + C::kCells);
+  BrickCells bc{cval, 1, reinterpret_cast<uint32_t*>(wbase + C::kRows), reinterpret_cast<uint32_t*>(wbase + C::kRows) + 65};
+  const DecWave4 dw{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(bitstream), 0, (int)(bs_words * 4u), (int)kBufRsrcW3),
+                    reinterpret_cast<uint32_t*>(wbase) + lane, tile, (uint32_t)bklen, lane};
+  constexpr uint32_t W = 256;
+  const uint32_t nw = gridDim.x * (blockDim.x >> 6);
+  const uint32_t nitems = box.bnx * box.bny * box.bnz;
+  const uint32_t ry = (uint32_t)lane >> 3, rz = (uint32_t)lane & 7u;
+  const uint32_t xend = box.ox + box.ex;  // one past the box's last column
+  BPROF(unsigned long long pc[16] = {}; unsigned long long tk = __builtin_readcyclecounter(), tp = tk;)
+
+  struct Next {
+    uint32_t nbit, entry, cb, ce;
+    bool live;
+  };
+  auto fetch = [&](uint32_t i) {
+    Next x{0, 0, 0, 0, false};
+    if (i >= nitems) return x;
+    const uint32_t bx = box.blx + i % box.bnx, t = i / box.bnx, by = box.bly + t % box.bny, bz = box.blz + t / box.bny;
+    x.live = by * 8 + ry < ly && bz * 8 + rz < lz;
+    if (x.live) {
+      const size_t c = ((size_t)(bz * 8 + rz) * ly + (by * 8 + ry)) * nbx + bx;
+      x.nbit = par_nbit[c], x.entry = par_entry[c];
+    }
+    if (ol.ncell) {
+      const uint32_t b = (bz * nby + by) * nbx + bx;
+      x.cb = ol.bstart[b], x.ce = ol.bstart[b + 1];
+    }
+    return x;
+  };
+  u32x4 first[2];
+  uint2 pcell[2];
+  auto prefetch = [&](const Next& x) {
+    first[0] = __builtin_amdgcn_raw_buffer_load_b128(dw.rbits, (int)(x.live ? x.entry * 4u : kOOB), 0, 0);
+    first[1] = __builtin_amdgcn_raw_buffer_load_b128(dw.rbits, (int)(x.live ? x.entry * 4u + 16u : kOOB), 0, 0);
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      const uint32_t j = x.cb + (uint32_t)lane + 64u * k;
+      pcell[k] = j < x.ce ? make_uint2(ol.cells[2 * (size_t)j], ol.cells[2 * (size_t)j + 1]) : make_uint2(0, 0);
+    }
+  };
+  const uint32_t i0 = (uint32_t)wid * gridDim.x + blockIdx.x;
+  Next nx = fetch(i0);  // (lands while the tables are built)
+  hfd::build_tab4(tb, revbook, bklen);
+  const hfd::DecRegs4 rg = hfd::load_dec_regs4(tb);
+  prefetch(nx);
+  for (uint32_t item = i0; item < nitems; item += nw) {
+    const uint32_t bx = box.blx + item % box.bnx, t = item / box.bnx, by = box.bly + t % box.bny, bz = box.blz + t / box.bny;
+    const uint32_t x0 = bx * W, y0 = by * 8, z0 = bz * 8;
+    const bool live = y0 + ry < ly && z0 + rz < lz;
+    const Next cur = nx;
+    const uint32_t nbit = live ? cur.nbit : 0u;
+    const uint32_t vbase = (live ? cur.entry : 0u) * 4u;
+    const u32x4 f2[2] = {first[0], first[1]};
+    const uint2 cp[2] = {pcell[0], pcell[1]};
+    // blocks of this brick that reach into the box's columns or lie left of them: 1..4
+    const uint32_t nblk = xend - x0 >= W ? W / BLK : (xend - x0 + BLK - 1) / BLK;
+    const uint32_t nc = cur.ce - cur.cb;
+    // the brick's outlier cells [cb, ce): per-row counts -> row starts; values into LDS
+    auto pro = [&]() {
+      bc.row_start[lane] = 0;
+      hfd::wave_sync();
+      for (uint32_t j = (uint32_t)lane; j < nc; j += 64) {
+        const uint2 cell = j < 64u    ? cp[0]
+                           : j < 128u ? cp[1]
+                                      : make_uint2(ol.cells[2 * (size_t)(cur.cb + j)], ol.cells[2 * (size_t)(cur.cb + j) + 1]);
+        const uint32_t yz = cell.y / lx;  // y + ly z
+        atomicAdd(&bc.row_start[((yz % ly) & 7u) * 8u + ((yz / ly) & 7u)], 1u);
+        if (nc <= kCellCap) cval[j] = cell.x;
+      }
+      hfd::wave_sync();
+      const uint32_t cr = bc.row_start[lane];
+      const uint32_t incl = hfd::wave_incl_scan(cr);
+      bc.row_start[lane] = incl - cr;
+      if (lane == 63) bc.row_start[64] = incl;
+      bc.carry[lane] = 0;
+      bc.val = nc <= kCellCap ? cval : ol.cells + 2 * (size_t)cur.cb;
+      bc.vstride = nc <= kCellCap ? 1u : 2u;
+    };
+    auto recon = [&](int blk) {
+      if (blk == (int)nblk - 1) prefetch(nx);  // the next brick (fetched during this block)
+      const uint32_t xb = x0 + (uint32_t)blk * BLK;
+      // a block left of the box stores nothing; its zero codes still consume the rows' cells
+      if (xb + BLK <= box.ox && nc == 0) return;
+      // rows and planes up to the box's (and the field's) far faces: the sums never look ahead
+      const uint32_t nyv = min(min(8u, ly - y0), box.oy + box.ey - y0), nzv = min(min(8u, lz - z0), box.oz + box.ez - z0);
+      const RegionClip rc{xb, y0, z0, box.ox, box.oy, box.oz, box.ex, box.ey, box.ez};
+      recon_block<T, false, false, C::TP, true, true>(tile, out, 0, 0, nyv, nzv, 0, r, ebx2, lane, &bc, &rc);
+    };
+    auto blk_start = [&](int blk) {
+      if (blk == (int)nblk - 1) nx = fetch(item + nw);
+    };
+    decode_chunks4<BLK, C::TP>(tb, rg, dw, live, vbase, nbit, nblk * BLK, pro, blk_start, recon BPROF_A4, nblk * BLK, f2);
+  }
 }
 // ---- 1-D: fused decode + reconstruct -------------------------------------------------------
 // A wave owns a unit of 64 tiles of 1024 (4 chunks of 256 each); lane l owns tile 64 u + l and
@@ -3234,6 +3379,41 @@ int launch_brick_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t 
   return (int)hipGetLastError();
 }
 
+RegionBox region_box(uint32_t ox, uint32_t oy, uint32_t oz, uint32_t ex, uint32_t ey, uint32_t ez, uint32_t W)
+{
+  RegionBox b{ox, oy, oz, ex, ey, ez, ox / W, oy / 8, oz / 8, 0, 0, 0};
+  b.bnx = (ox + ex - 1) / W - b.blx + 1;
+  b.bny = (oy + ey - 1) / 8 - b.bly + 1;
+  b.bnz = (oz + ez - 1) / 8 - b.blz + 1;
+  return b;
+}
+
+template <typename T>
+int launch_brick_region(const BrickLaunch& L, const uint32_t* bitstream, size_t bs_words, const uint8_t* revbook,
+                        int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, T* out_box, double eb,
+                        int radius, const BrickOutliers& ol, const uint32_t (&o)[3], const uint32_t (&e)[3],
+                        hipStream_t st)
+{
+  const BrickGeom& g = L.g;
+  // the box lies inside the field, so its covering bricks lie inside the brick grid
+  if (!g.ok || g.ndim != 3 || g.W != 256 || bs_words >= (1ull << 30) || bklen < 1 || bklen > kMaxBklen || !e[0] ||
+      !e[1] || !e[2] || o[0] >= L.lx || e[0] > L.lx - o[0] || o[1] >= L.ly || e[1] > L.ly - o[1] || o[2] >= L.lz ||
+      e[2] > L.lz - o[2])
+    return (int)hipErrorInvalidValue;
+  const RegionBox box = region_box(o[0], o[1], o[2], e[0], e[1], e[2], (uint32_t)g.W);
+  const T ebx2 = (T)(eb * 2);  // lrz_x.cuhip.inl:432
+  const T r = (T)radius;
+  typedef Dec3Cfg<64> C;
+  const uint32_t items = box.bnx * box.bny * box.bnz;
+  // one brick per CU while they last (wave 0 of each workgroup), then one per SIMD, ...: a
+  // region is bound by one brick's serial walk, not by throughput
+  const uint32_t grid = std::max(1u, std::min((uint32_t)L.ncu, items));
+  const size_t lds = (size_t)C::kWaves * C::kWaveBytes;  // dynamic part
+  k_brick3_region<T><<<grid, 64 * C::kWaves, lds, st>>>(bitstream, (uint32_t)bs_words, revbook, bklen, par_nbit,
+                                                        par_entry, out_box, L.lx, L.ly, L.lz, ebx2, r, g.nbx, g.nby,
+                                                        ol, box);
+  return (int)hipGetLastError();
+}
 
 int launch_chunk_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t bs_words, const uint8_t* revbook,
                         int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, uint16_t* codes, size_t n,
@@ -3273,7 +3453,10 @@ extern "C" int psz_amd_debug_brick_profile(unsigned long long* host, int reset)
                                     const HostPub&);                                                                \
   template int launch_brick_decode<T>(const BrickLaunch&, const uint32_t*, size_t, const uint8_t*, int,            \
                                       const uint32_t*, const uint32_t*, T*, double, int, bool, const BrickOutliers&, \
-                                      hipStream_t);
+                                      hipStream_t);                                                                \
+  template int launch_brick_region<T>(const BrickLaunch&, const uint32_t*, size_t, const uint8_t*, int,            \
+                                      const uint32_t*, const uint32_t*, T*, double, int, const BrickOutliers&,     \
+                                      const uint32_t(&)[3], const uint32_t(&)[3], hipStream_t);
 INST(float)
 INST(double)
 #undef INST

@@ -2,6 +2,7 @@
 //
 //   cusz -t f32 -m abs -e 1e-4 -l 512x512x512 -z -i field.f32      -> field.f32.cusza
 //   cusz -x -i field.f32.cusza [--origin field.f32]                -> field.f32.cuszx
+//   cusz -x -i field.f32.cusza --region 0,0,100:512,512,1          -> field.f32.cuszx (the box only)
 //
 // Archive file = the device archive verbatim (this build writes the 176-B psz_header into
 // the device archive itself; the reference patches it in on the host, cli.cc:112-118).
@@ -10,6 +11,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -53,7 +55,40 @@ static void usage()
 {
   std::printf(
       "usage: cusz -z -t f32|f64 -m abs|rel|r2r -e EB -l X[xY[xZ]] -i FILE [-p lrz|lrz-zz] [-R time,cr]\n"
-      "       cusz -x -i FILE.cusza [--origin FILE] [-R time] [-S write2disk]\n");
+      "       cusz -x -i FILE.cusza [--origin FILE] [-R time] [-S write2disk]\n"
+      "               [--region X0[,Y0[,Z0]]:EX[,EY[,EZ]]]  (decode only this box, in elements)\n");
+}
+
+// "x0[,y0[,z0]]:ex[,ey[,ez]]" -> origin (missing axes 0) and extent (missing axes 1)
+static bool parse_region(const char* s, psz_len* origin, psz_len* extent)
+{
+  size_t v[2][3] = {{0, 0, 0}, {1, 1, 1}};
+  for (int part = 0; part < 2; part++) {
+    for (int k = 0;; k++) {
+      char* end;
+      if (k == 3 || *s < '0' || *s > '9') return false;
+      v[part][k] = (size_t)std::strtoull(s, &end, 10);
+      s = end;
+      if (*s != ',') break;
+      s++;
+    }
+    if (*s != (part == 0 ? ':' : '\0')) return false;
+    s++;
+  }
+  *origin = psz_len{v[0][0], v[0][1], v[0][2]};
+  *extent = psz_len{v[1][0], v[1][1], v[1][2]};
+  return true;
+}
+
+// the same box of a whole field on the host (the --origin comparison of a region decode)
+template <typename T>
+static std::vector<T> crop(const T* f, psz_len l, psz_len o, psz_len e)
+{
+  std::vector<T> b(e.x * e.y * e.z);
+  for (size_t z = 0; z < e.z; z++)
+    for (size_t y = 0; y < e.y; y++)
+      std::memcpy(&b[(z * e.y + y) * e.x], f + ((o.z + z) * l.y + o.y + y) * l.x + o.x, e.x * sizeof(T));
+  return b;
 }
 
 template <typename T>
@@ -116,6 +151,20 @@ int main(int argc, char** argv)
     if (!std::strcmp(argv[i], "-v") || !std::strcmp(argv[i], "--version")) return psz_version(), 0;
     if (!std::strcmp(argv[i], "-V") || !std::strcmp(argv[i], "--versioninfo")) return psz_versioninfo(), 0;
   }
+  // --region is this build's own flag: taken out before the reference's parser sees argv
+  bool region = false;
+  psz_len r_origin{0, 0, 0}, r_extent{1, 1, 1};
+  for (int i = 1; i < argc; i++) {
+    if (std::strcmp(argv[i], "--region")) continue;
+    if (i + 1 >= argc || !parse_region(argv[i + 1], &r_origin, &r_extent)) {
+      std::fprintf(stderr, "[cusz] --region needs X0[,Y0[,Z0]]:EX[,EY[,EZ]]\n");
+      return usage(), 1;
+    }
+    region = true;
+    for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+    argc -= 2;
+    i--;
+  }
   psz_ctx* ctx = pszctx_default_values();
   pszctx_create_from_argv(ctx, argc, argv);
   if (ctx->last_error != PSZ_SUCCESS) return usage(), 1;
@@ -127,6 +176,10 @@ int main(int argc, char** argv)
   CK(hipStreamCreate(&st));
   using clk = std::chrono::steady_clock;
 
+  if (region && !ctx->cli->task_reconstruct) {
+    std::fprintf(stderr, "[cusz] --region goes with -x\n");
+    return usage(), 1;
+  }
   if (ctx->cli->task_construct) {
     const psz_header* h = ctx->header;
     const size_t n = h->len.x * h->len.y * h->len.z;
@@ -184,10 +237,49 @@ int main(int argc, char** argv)
     uint8_t* d_arch;
     void* d_out;
     CK(hipMalloc(&d_arch, arch.size()));
-    CK(hipMalloc(&d_out, n * es));
+    psz_amd_region_info plan{};
+    if (region && psz_amd_region_plan(&h, r_origin, r_extent, &plan) != PSZ_SUCCESS) {
+      std::fprintf(stderr, "[cusz] --region: the box is empty or leaves the %zux%zux%zu field\n", h.len.x, h.len.y, h.len.z);
+      return 1;
+    }
+    CK(hipMalloc(&d_out, (region ? plan.elems : n) * es));
     CK(hipMemcpy(d_arch, arch.data(), arch.size(), hipMemcpyHostToDevice));
     psz_resource* m = psz_create_resource_manager_from_header(&h, st);
     if (!m) return std::fprintf(stderr, "[cusz] cannot create resource manager\n"), 1;
+    if (region) {  // only the box is decoded and written
+      const size_t nb = r_extent.x * r_extent.y * r_extent.z;
+      auto t0 = clk::now();
+      int s = h.dtype == F4 ? psz_amd_decompress_region_float(m, d_arch, arch.size(), r_origin, r_extent, (float*)d_out)
+                            : psz_amd_decompress_region_double(m, d_arch, arch.size(), r_origin, r_extent, (double*)d_out);
+      CK(hipStreamSynchronize(st));
+      double wall = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+      if (s != PSZ_SUCCESS) return std::fprintf(stderr, "[cusz] region decompress failed with status %d\n", s), 1;
+      psz_amd_region_info ri;
+      psz_amd_last_region(m, &ri);
+      std::vector<char> out(nb * es);
+      CK(hipMemcpy(out.data(), d_out, nb * es, hipMemcpyDeviceToHost));
+      std::string base(ctx->cli->file_input);
+      if (base.size() > 6 && base.substr(base.size() - 6) == ".cusza") base = base.substr(0, base.size() - 6);
+      if (!ctx->cli->skip_tofile && !write_file(base + ".cuszx", out.data(), out.size())) return 1;
+      std::printf("decompressed region %zu,%zu,%zu:%zux%zux%zu of %s -> %s.cuszx (%zu bytes, %s, %zu bricks)\n",
+                  r_origin.x, r_origin.y, r_origin.z, r_extent.x, r_extent.y, r_extent.z, ctx->cli->file_input,
+                  base.c_str(), nb * es, ri.path == PSZ_AMD_REGION_FUSED ? "fused" : "fallback", ri.bricks);
+      if (ctx->cli->report_time) std::printf("time: region decompress %.3f ms (wall)\n", wall);
+      if (ctx->cli->file_compare[0]) {
+        std::vector<char> orig;
+        if (read_file(ctx->cli->file_compare, orig) && orig.size() >= n * es) {
+          if (h.dtype == F4)
+            quality(crop((const float*)orig.data(), h.len, r_origin, r_extent).data(), (const float*)out.data(), nb, h.rc.eb);
+          else
+            quality(crop((const double*)orig.data(), h.len, r_origin, r_extent).data(), (const double*)out.data(), nb, h.rc.eb);
+        }
+      }
+      psz_release_resource(m);
+      CK(hipFree(d_arch));
+      CK(hipFree(d_out));
+      CK(hipStreamDestroy(st));
+      return 0;
+    }
     psz_amd_enable_timing(m, 1);
     auto t0 = clk::now();
     int s = h.dtype == F4 ? psz_decompress_float(m, d_arch, arch.size(), (float*)d_out)

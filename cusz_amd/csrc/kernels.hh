@@ -355,6 +355,24 @@ int launch_brick_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t 
                         int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, T* out, double eb, int radius,
                         bool zz, const BrickOutliers& ol, hipStream_t st);
 
+// Region decode (3-D brick fields, Lorenzo, ranked cells -- the caller has read the bounds pass's
+// verdict): the box of e elements at o, decoded from its covering bricks only into out_box, a
+// compact array of e (x fastest).  region_box: the covering bricks (lo, n) of a box, brick width W.
+struct RegionBox {
+  uint32_t ox, oy, oz, ex, ey, ez;        // box, in elements
+  uint32_t blx, bly, blz, bnx, bny, bnz;  // covering bricks: first, count
+};
+RegionBox region_box(uint32_t ox, uint32_t oy, uint32_t oz, uint32_t ex, uint32_t ey, uint32_t ez, uint32_t W);
+template <typename T>
+int launch_brick_region(const BrickLaunch& L, const uint32_t* bitstream, size_t bs_words, const uint8_t* revbook,
+                        int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, T* out_box, double eb,
+                        int radius, const BrickOutliers& ol, const uint32_t (&o)[3], const uint32_t (&e)[3],
+                        hipStream_t st);
+// out_box[(z ey + y) ex + x] = field[((oz + z) ly + oy + y) lx + ox + x] (the region fallback)
+template <typename T>
+int launch_crop_box(const T* field, size_t lx, size_t ly, const size_t (&o)[3], const size_t (&e)[3], T* out_box,
+                    hipStream_t st);
+
 // min / max (Rel mode, extrema.cuhip.inl:86-208), writes {min, max} as doubles
 template <typename T>
 int launch_extrema(const T* in, size_t n, double* d_minmax, unsigned int* d_scratch, hipStream_t st);

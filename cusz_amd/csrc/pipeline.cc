@@ -50,6 +50,38 @@ static int ndim_of(psz_len l)
   return 3;
 }
 
+// What a region decode of an archive with header h touches (psz_amd_region_plan): the header's
+// share of Pipeline::decompress_region's path choice, and the covering bricks.
+static int region_plan(const psz_header* h, psz_len o, psz_len e, psz_amd_region_info* out)
+{
+  const psz_len l = h->len;
+  if (!l.x || !l.y || !l.z || !e.x || !e.y || !e.z || o.x >= l.x || e.x > l.x - o.x || o.y >= l.y ||
+      e.y > l.y - o.y || o.z >= l.z || e.z > l.z - o.z)
+    return PSZ_AMD_ERR_INVALID_ARG;
+  psz_amd_region_info r{};
+  r.elems = e.x * e.y * e.z;
+  const int nd = ndim_of(l);
+  const BrickGeom g = brick_geom(nd, l.x, l.y, l.z, h->dtype == F8 ? 8 : 4);
+  // (the decoder finds a brick row's chunk by its position: one chunk per row of 256)
+  const bool fused = g.ok && nd == 3 && h->pipeline.predictor == Lorenzo && h->vle_sublen == g.W &&
+                     h->vle_pardeg > 0 && (uint32_t)h->vle_pardeg == g.nchunks && 2 * (int)h->rc.radius <= kMaxBklen;
+  if (fused) {
+    const RegionBox b = region_box((uint32_t)o.x, (uint32_t)o.y, (uint32_t)o.z, (uint32_t)e.x, (uint32_t)e.y,
+                                   (uint32_t)e.z, (uint32_t)g.W);
+    r.path = PSZ_AMD_REGION_FUSED;
+    r.brick_lo = psz_len{b.blx, b.bly, b.blz};
+    r.brick_n = psz_len{b.bnx, b.bny, b.bnz};
+    r.bricks = (size_t)b.bnx * b.bny * b.bnz;
+    r.chunks = r.bricks * 64;
+  }
+  else {
+    r.path = PSZ_AMD_REGION_FALLBACK;
+    r.chunks = h->vle_pardeg > 0 ? (size_t)h->vle_pardeg : 0;
+  }
+  *out = r;
+  return PSZ_SUCCESS;
+}
+
 // Chunk length (vle_sublen).  The reference sizes chunks for one encode thread per chunk on
 // maxThreadsPerBlock * nSM / 4 threads (libphf.cc:26-70, which notes "ROCm GPUs should use
 // different constants").  Here the decoder is the consumer that needs the parallelism: one lane
@@ -99,6 +131,9 @@ struct Pipeline {
   uint32_t* d_x1d = nullptr;      // 1-D decompression: per-brick first outlier cell + unsorted flag
   uint32_t cell_epoch = 0;        // tags the unsorted flag of the current decompress (never 0)
   uint32_t next_cell_epoch() { return cell_epoch = cell_epoch + 1 ? cell_epoch + 1 : 1; }
+  void* d_region_field = nullptr;  // region fallback: the whole field (allocated on first use)
+  psz_amd_region_info last_region{};
+  bool has_last_region = false;
   size_t spl_x_words = 0;
   int sublen = 256, pardeg = 1;
   int user_sublen = 0;
@@ -169,6 +204,7 @@ struct Pipeline {
   void release()
   {
     if (d_shist) (void)hipFree(d_shist), d_shist = nullptr;
+    if (d_region_field) (void)hipFree(d_region_field), d_region_field = nullptr;
     for (void* p : {(void*)d_codes, (void*)d_hist, (void*)d_book, (void*)d_slots, (void*)d_brick_cnt,
                     (void*)d_brick_off, (void*)d_spill, (void*)d_small, (void*)d_status, (void*)d_archive,
                     (void*)d_enc_temp, (void*)d_spl_slots, (void*)d_spl_cnt, (void*)d_spl_off, (void*)d_spl_x, (void*)d_spl_sps,
@@ -1109,6 +1145,63 @@ struct Pipeline {
     return PSZ_SUCCESS;
   }
 
+  // The box of e elements at o into `out` (cusz_amd.h psz_amd_decompress_region_*).  FUSED: only
+  // the covering bricks are decoded (brick.hip k_brick3_region), which needs the fused 3-D
+  // decoder's conditions and ranked outlier cells -- the bounds pass's verdict is the one word
+  // read back here, before the decode is queued.  FALLBACK: the whole field into a scratch
+  // field, then the box copied out.
+  template <typename T>
+  int decompress_region(const psz_header* h, const uint8_t* in, psz_len o, psz_len e, T* out)
+  {
+    pend.active = false;  // as decompress
+    const psz_predictor pred = h->pipeline.predictor;
+    if (pred != Lorenzo && pred != LorenzoZigZag && pred != Spline) return PSZ_ABORT_NO_SUCH_PREDICTOR;
+    if (h->len.x != len.x || h->len.y != len.y || h->len.z != len.z) return PSZ_ABORT_UNSUPPORTED_DIMENSION;
+    psz_amd_region_info info;
+    if (const int s = region_plan(h, o, e, &info)) return s;
+    bool fused = info.path == PSZ_AMD_REGION_FUSED && bl.g.ok && decoder == 0;
+    BrickOutliers bo;
+    if (fused && h->splen) {
+      const uint32_t* cells = reinterpret_cast<const uint32_t*>(in + h->entry[PSZHEADER_SPFMT]);
+      const uint32_t nb = bl.g.nbricks;
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_cell_bounds(bl, cells, h->splen, d_x1d, d_x1d + nb + 1,
+                                                              next_cell_epoch(), stream));
+      uint32_t word = 0;
+      CUSZ_AMD_HIP_CHECK(hipMemcpyAsync(&word, d_x1d + nb + 1, 4, hipMemcpyDeviceToHost, stream));
+      CUSZ_AMD_HIP_CHECK(hipStreamSynchronize(stream));
+      fused = word != cell_epoch;
+      bo = BrickOutliers{cells, (size_t)h->splen, d_x1d, d_x1d + nb + 1, cell_epoch};
+    }
+    if (fused) {
+      const int bklen = 2 * h->rc.radius;
+      const size_t phf_off = h->entry[PSZHEADER_ENCODED];
+      const size_t rvbk = rvbk_bytes(bklen);
+      const int pd = h->vle_pardeg;  // (== bl.g.nchunks: region_plan)
+      const uint8_t* phf = in + phf_off;
+      const size_t bits_off = phf_off + 128 + rvbk + 8 * (size_t)pd;
+      const size_t total = h->entry[PSZHEADER_ENC_PASS2_END];
+      const size_t bs_words = total > bits_off ? (total - bits_off) / 4 : 0;
+      const uint32_t o3[3] = {(uint32_t)o.x, (uint32_t)o.y, (uint32_t)o.z}, e3[3] = {(uint32_t)e.x, (uint32_t)e.y, (uint32_t)e.z};
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_region<T>(
+          bl, reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 8 * (size_t)pd), bs_words, phf + 128, bklen,
+          reinterpret_cast<const uint32_t*>(phf + 128 + rvbk), reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 4 * (size_t)pd),
+          out, h->rc.eb, h->rc.radius, bo, o3, e3, stream));
+    }
+    else {
+      if (!d_region_field) CUSZ_AMD_HIP_CHECK(hipMalloc(&d_region_field, n * sizeof(T)));
+      if (const int s = decompress<T>(h, in, static_cast<T*>(d_region_field))) return s;
+      const size_t o3[3] = {o.x, o.y, o.z}, e3[3] = {e.x, e.y, e.z};
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_crop_box<T>(static_cast<const T*>(d_region_field), len.x, len.y, o3, e3, out, stream));
+      const size_t elems = info.elems;
+      info = psz_amd_region_info{};
+      info.path = PSZ_AMD_REGION_FALLBACK, info.elems = elems;
+      info.chunks = h->vle_pardeg > 0 ? (size_t)h->vle_pardeg : 0;
+    }
+    last_region = info;
+    has_last_region = true;
+    return PSZ_SUCCESS;
+  }
+
   // decode -> (outlier buckets) -> spline reconstruct; the archive's outlier cells hold codes
   template <typename T>
   int decompress_spline(const psz_header* h, const uint8_t* in, T* out)
@@ -1369,22 +1462,39 @@ int psz_amd_compress_finish(psz_resource* m, const uint32_t* d_hist, psz_header*
 
 }  // extern "C"
 
+// the header's segment table must be ordered and fit the archive the caller passed
 template <typename T>
-static int decompress_impl(psz_resource* m, uint8_t* in, size_t in_len, T* out)
+static int check_archive(const psz_resource* m, size_t in_len)
 {
-  if (!m || !in || !out) return PSZ_AMD_ERR_INVALID_ARG;
-  Pipeline* p = cusz_amd::P(m);
-  // the header's segment table must be ordered and fit the archive the caller passed
   const uint32_t* e = m->header->entry;
   for (int k = 1; k <= PSZHEADER_ENC_PASS2_END; k++)
     if (e[k] < e[k - 1]) return PSZ_AMD_ERR_BAD_ARCHIVE;
   if (in_len && e[PSZHEADER_ENC_PASS2_END] > in_len) return PSZ_AMD_ERR_BAD_ARCHIVE;
   if ((size_t)e[PSZHEADER_ENC_PASS1_END] - e[PSZHEADER_SPFMT] != 8 * m->header->splen) return PSZ_AMD_ERR_BAD_ARCHIVE;
   if ((sizeof(T) == 4) != (m->header->dtype == F4)) return PSZ_ABORT_UNSUPPORTED_TYPE;
+  return PSZ_SUCCESS;
+}
+
+template <typename T>
+static int decompress_impl(psz_resource* m, uint8_t* in, size_t in_len, T* out)
+{
+  if (!m || !in || !out) return PSZ_AMD_ERR_INVALID_ARG;
+  Pipeline* p = cusz_amd::P(m);
+  if (const int c = check_archive<T>(m, in_len)) return c;
   CUSZ_AMD_HIP_CHECK(hipSetDevice(p->device));
   int s = p->decompress<T>(m->header, in, out);
   if (s == PSZ_SUCCESS && p->timing) p->collect_decompress_times();
   return s;
+}
+
+template <typename T>
+static int decompress_region_impl(psz_resource* m, uint8_t* in, size_t in_len, psz_len o, psz_len e, T* out)
+{
+  if (!m || !in || !out) return PSZ_AMD_ERR_INVALID_ARG;
+  Pipeline* p = cusz_amd::P(m);
+  if (const int c = check_archive<T>(m, in_len)) return c;
+  CUSZ_AMD_HIP_CHECK(hipSetDevice(p->device));
+  return p->decompress_region<T>(m->header, in, o, e, out);
 }
 
 extern "C" {
@@ -1397,6 +1507,33 @@ int psz_decompress_float(psz_resource* m, uint8_t* in, size_t const in_len, floa
 int psz_decompress_double(psz_resource* m, uint8_t* in, size_t const in_len, double* out)
 {
   return decompress_impl<double>(m, in, in_len, out);
+}
+
+int psz_amd_region_plan(const psz_header* h, psz_len origin, psz_len extent, psz_amd_region_info* out)
+{
+  if (!h || !out) return PSZ_AMD_ERR_INVALID_ARG;
+  return cusz_amd::region_plan(h, origin, extent, out);
+}
+
+int psz_amd_decompress_region_float(psz_resource* m, uint8_t* in, size_t in_len, psz_len origin, psz_len extent,
+                                    float* out)
+{
+  return decompress_region_impl<float>(m, in, in_len, origin, extent, out);
+}
+
+int psz_amd_decompress_region_double(psz_resource* m, uint8_t* in, size_t in_len, psz_len origin, psz_len extent,
+                                     double* out)
+{
+  return decompress_region_impl<double>(m, in, in_len, origin, extent, out);
+}
+
+int psz_amd_last_region(psz_resource* m, psz_amd_region_info* out)
+{
+  Pipeline* p = cusz_amd::P(m);
+  if (!p || !out) return PSZ_AMD_ERR_INVALID_ARG;
+  if (!p->has_last_region) return PSZ_AMD_ERR_STATE;
+  *out = p->last_region;
+  return PSZ_SUCCESS;
 }
 
 // =========================================================================================

@@ -294,7 +294,37 @@ __global__ void __launch_bounds__(256) k_gate_upload(XferRegions r, const uint32
     for (int i = blockIdx.x * 256 + threadIdx.x; i < r.nwords[k]; i += gridDim.x * 256) r.dst[k][i] = r.src[k][i];
 }
 
+// A box out of a field (the region decode's fallback): one workgroup per run of box rows, threads
+// along x.
+template <typename T>
+__global__ void __launch_bounds__(256) k_crop_box(const T* __restrict__ field, size_t lx, size_t ly, size_t ox,
+                                                  size_t oy, size_t oz, size_t ex, size_t ey, size_t nrows,
+                                                  T* __restrict__ out)
+{
+  for (size_t row = blockIdx.x; row < nrows; row += gridDim.x) {  // row = z ey + y of the box
+    const size_t y = row % ey, z = row / ey;
+    const T* src = field + ((oz + z) * ly + oy + y) * lx + ox;
+    T* dst = out + row * ex;
+    for (size_t x = threadIdx.x; x < ex; x += 256) dst[x] = src[x];
+  }
+}
+
 }  // namespace
+
+template <typename T>
+int launch_crop_box(const T* field, size_t lx, size_t ly, const size_t (&o)[3], const size_t (&e)[3], T* out_box,
+                    hipStream_t st)
+{
+  const size_t nrows = e[1] * e[2];
+  if (!nrows || !e[0]) return (int)hipErrorInvalidValue;
+  const uint32_t grid = (uint32_t)std::min<size_t>(nrows, 4096);
+  k_crop_box<T><<<grid, 256, 0, st>>>(field, lx, ly, o[0], o[1], o[2], e[0], e[1], nrows, out_box);
+  return (int)hipGetLastError();
+}
+template int launch_crop_box<float>(const float*, size_t, size_t, const size_t (&)[3], const size_t (&)[3], float*,
+                                    hipStream_t);
+template int launch_crop_box<double>(const double*, size_t, size_t, const size_t (&)[3], const size_t (&)[3], double*,
+                                     hipStream_t);
 
 int launch_gate_upload(const XferRegions& r, const uint32_t* gate, uint32_t epoch, unsigned int* timeout,
                        hipStream_t st)

@@ -152,6 +152,49 @@ int psz_amd_merge_archives(const uint8_t* const* parts, const size_t* part_bytes
                            const size_t* elem_offsets, psz_len full_len, uint8_t* out, size_t out_cap,
                            size_t* out_bytes);
 
+/* ---- region-of-interest decompression (the reference reconstructs whole fields only) ----
+ * Decode the box of `extent` elements at `origin` (both in elements, any alignment, extent >= 1
+ * per axis; unused axes: origin 0, extent 1) of an archive of the manager's whole field into
+ * OUT_d_box, a compact device array of extent.x * extent.y * extent.z elements (x fastest).  It
+ * need not be zeroed and nothing outside it is written.  The result is bit-identical to the same
+ * box of psz_decompress_*.  Header, length, dtype and archive checks are those of
+ * psz_decompress_* (PSZ_ABORT_UNSUPPORTED_TYPE, PSZ_AMD_ERR_BAD_ARCHIVE, ...); a box that is
+ * empty or leaves the field: PSZ_AMD_ERR_INVALID_ARG, nothing written.
+ *  FUSED: 3-D brick-eligible fields (x a multiple of the brick width 256), Lorenzo, chunk length
+ *    256, default decoder, outlier cells in this compressor's order: only the 256 x 8 x 8 bricks
+ *    that cover the box are decoded, each whole (64 Huffman chunks), and only the box is stored.
+ *  FALLBACK: everything else (1-D, 2-D, other shapes or chunk lengths, ZigZag, Spline, cells in
+ *    another order, a forced LANE / WAVE decoder): the whole field is decompressed into a scratch
+ *    field the manager allocates on first use, and the box copied out.  Correct everywhere, not
+ *    fast.
+ * The work is queued on the manager's stream.  When the archive has outlier cells, a FUSED
+ * candidate waits once for a 4-byte read-back (are the cells in brick order?) before its decode
+ * is queued; no other host synchronisation.  Like psz_decompress_*, a region call invalidates a
+ * pending psz_amd_compress_scan_*. */
+#define PSZ_AMD_REGION_FUSED 0
+#define PSZ_AMD_REGION_FALLBACK 1
+typedef struct psz_amd_region_info {
+  int path;                  /* PSZ_AMD_REGION_FUSED or PSZ_AMD_REGION_FALLBACK               */
+  psz_len brick_lo, brick_n; /* covering brick box: first brick, bricks per axis (FUSED), else zeros */
+  size_t bricks;             /* bricks decoded (FALLBACK: 0, the whole archive is decoded)    */
+  size_t chunks;             /* Huffman chunks decoded (FUSED: 64 per brick; FALLBACK: all)   */
+  size_t elems;              /* extent.x * extent.y * extent.z                                */
+} psz_amd_region_info;
+
+/* Host only, no GPU: validates the box against the header's field and says what a region decode
+ * of such an archive touches.  The path is the header's verdict; the device-side checks (the
+ * manager's decoder knob, the cells' order) can still turn FUSED into FALLBACK: see
+ * psz_amd_last_region. */
+int psz_amd_region_plan(const psz_header* h, psz_len origin, psz_len extent, psz_amd_region_info* out);
+
+int psz_amd_decompress_region_float(psz_resource* m, uint8_t* IN_d_compressed, size_t IN_bytes, psz_len origin,
+                                    psz_len extent, float* OUT_d_box);
+int psz_amd_decompress_region_double(psz_resource* m, uint8_t* IN_d_compressed, size_t IN_bytes, psz_len origin,
+                                     psz_len extent, double* OUT_d_box);
+/* What the last successful region call on this manager did (the path taken after the device-side
+ * checks); PSZ_AMD_ERR_STATE before the first one. */
+int psz_amd_last_region(psz_resource* m, psz_amd_region_info* out);
+
 const char* psz_amd_version(void);
 
 /* The device codebook (no host round trip; NOT the reference's heap order, the same total bit
