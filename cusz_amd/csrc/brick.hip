@@ -254,12 +254,22 @@ __device__ __forceinline__ uint32_t pass1_brick(uint32_t j, const BrickSample& s
   return g * sp.stride + (p < o ? p : p + 1);
 }
 
+// What only the wave completing the codebook sample needs of BrickSample.  The 3-D kernel keeps it
+// in LDS, not in scalar registers live across the row loop (pass 1 spills scalars as it is).
+struct SamplePub {
+  uint32_t* dst;
+  uint32_t* flag;
+  uint32_t epoch, total;
+};
+
 // End of a pass-1 unit: outlier count, row mask, the unit's histogram as a u16 record (16-B
 // stores, 8 bins per lane; the wave's LDS copy is cleared) and into the workgroup histogram; a
 // sample brick also adds it to the codebook sample (global atomics) and then counts itself done.
+template <bool BY_VALUE>
 __device__ __forceinline__ void finish_unit(const OutlierSink& ol, const BrickCodes& bcs, uint32_t u, uint32_t cnt,
                                             uint64_t rowmask, uint32_t* s_hist, uint32_t* s_wg, uint16_t* bhist,
-                                            int hs, int lane, const BrickSample& sp, bool sample)
+                                            int hs, int bklen, int lane, const BrickSample& sp, const SamplePub& sb,
+                                            bool sample)
 {
   if (lane == 0) ol.brick_cnt[u] = cnt;
   if (lane == 0) bcs.rowmask[u] = rowmask;  // kUnitBricks == 1: unit = brick
@@ -289,17 +299,38 @@ __device__ __forceinline__ void finish_unit(const OutlierSink& ol, const BrickCo
   if (sample) {
     __builtin_amdgcn_s_waitcnt(0);  // this wave's sample atomics have completed
     uint32_t prev = 0;
-    // release / acquire at agent scope: the wave completing the sample sees every sample brick's
-    // atomics by the memory model, not only by the hardware's ordering (once per sample brick)
-    if (lane == 0) prev = __hip_atomic_fetch_add(sp.done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if ((uint32_t)__builtin_amdgcn_readfirstlane((int)prev) == sp.count - 1 && sp.pub_flag) {
-      // the sample is complete: this wave hands it to the host (agent-scope reads: every
-      // sample brick's atomics have completed before its count)
-      for (int i = lane; i < sp.bklen; i += 64)
-        sp.pub_dst[i] = __hip_atomic_load(sp.hist + i * kSampleBinStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // 3-D bricks (BY_VALUE; sb.total: the sample's element count, known from the shape): the count
+    // is relaxed, and the completing wave validates the sample by value.  Every bin only grows, by
+    // whole atomic adds, and the sample is complete exactly when its bins sum to sb.total -- so a
+    // read whose sum is sb.total has seen every sample brick's counts, by the atomicity and the
+    // coherence of each bin alone; nothing rests on the order in which another XCD's atomics become
+    // visible.  (A release per sample brick wrote back the XCD's L2, megabytes of dirty code rows,
+    // 248 times a pass: +27 us of pass 1.)  The wave re-reads until the sum matches; the bound
+    // (~0.1 s) only keeps a broken device from hanging the host.
+    // Linear bricks: release / acquire at agent scope per sample brick, so that the completing
+    // wave sees every sample brick's atomics by the memory model.
+    if (lane == 0)
+      prev = __hip_atomic_fetch_add(sp.hist + kMaxBklen * kSampleBinStride, 1u, BY_VALUE ? __ATOMIC_RELAXED : __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if ((uint32_t)__builtin_amdgcn_readfirstlane((int)prev) == sp.count - 1 && sb.flag) {
+      // the sample is complete: this wave hands it to the host (agent-scope reads).  The host
+      // pointers come out of LDS, so their address space is stated: as flat stores they would
+      // turn the row loop's counted vmcnt waits into waits for everything (measured: +40 us)
+      typedef __attribute__((address_space(1))) uint32_t global_u32;
+      global_u32* const pub_dst = (global_u32*)sb.dst;
+      global_u32* const pub_flag = (global_u32*)sb.flag;
+      for (uint32_t tries = 0; tries < (1u << 16); tries++) {
+        uint32_t sum = 0;
+        for (int i = lane; i < bklen; i += 64) {
+          const uint32_t v = __hip_atomic_load(sp.hist + i * kSampleBinStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          pub_dst[i] = v;
+          sum += v;
+        }
+        if (!BY_VALUE || readlane(hfd::wave_incl_scan(sum), 63) == sb.total) break;
+        __builtin_amdgcn_s_sleep(32);
+      }
       __threadfence_system();
       hfd::wave_sync();
-      if (lane == 0) __hip_atomic_store(sp.pub_flag, sp.pub_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (lane == 0) __hip_atomic_store(pub_flag, sb.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
 }
@@ -328,6 +359,8 @@ k_brick3_scan(const T* __restrict__ in, uint32_t lx, uint32_t ly, uint32_t lz, T
 {
   extern __shared__ uint32_t smem[];
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wid: uniform (SGPR)
+  SamplePub& sb = *reinterpret_cast<SamplePub*>(smem + (1 + kBrickWaves * kHistCopies) * kMaxBklen);  // after the histograms
+  if (threadIdx.x == 0) sb = SamplePub{sp.pub_dst, sp.pub_flag, sp.pub_epoch, sp.total};
   uint32_t* s_wg = smem;                                // workgroup histogram (-> global, once)
   uint32_t* s_hist = smem + (1 + wid * kHistCopies) * kMaxBklen;  // this wave's brick histogram
   for (int i = threadIdx.x; i < bklen; i += blockDim.x) s_wg[i] = 0;
@@ -460,7 +493,7 @@ k_brick3_scan(const T* __restrict__ in, uint32_t lx, uint32_t ly, uint32_t lz, T
         }
       }
     }
-    finish_unit(ol, bcs, u, cnt, rowmask, s_hist, s_wg, bhist, hs, lane, sp, sp.hist && it < sp.count);
+    finish_unit<true>(ol, bcs, u, cnt, rowmask, s_hist, s_wg, bhist, hs, bklen, lane, sp, sb, sp.hist && it < sp.count);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < bklen; i += blockDim.x) {
@@ -489,6 +522,7 @@ k_brick1_scan(const T* __restrict__ in, size_t n, T ebx2_r, T r, OutlierSink ol,
   static_assert(V == 4, "W = 256");
   extern __shared__ uint32_t smem[];
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const SamplePub sb{sp.pub_dst, sp.pub_flag, sp.pub_epoch, 0u};
   uint32_t* s_wg = smem;
   uint32_t* s_hist = smem + (1 + wid * kHistCopies) * kMaxBklen;
   for (int i = threadIdx.x; i < bklen; i += blockDim.x) s_wg[i] = 0;
@@ -637,7 +671,7 @@ k_brick1_scan(const T* __restrict__ in, size_t n, T ebx2_r, T r, OutlierSink ol,
         }
       }
     }
-    finish_unit(ol, bcs, u, cnt, rowmask, s_hist, s_wg, bhist, hs, lane, sp, sp.hist && it < sp.count);
+    finish_unit<false>(ol, bcs, u, cnt, rowmask, s_hist, s_wg, bhist, hs, bklen, lane, sp, sb, sp.hist && it < sp.count);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < bklen; i += blockDim.x) {
@@ -3100,10 +3134,11 @@ __global__ void __launch_bounds__(kFinishThreads) k_brick3_stream_finish(StreamA
 
 }  // namespace
 
-BrickSample brick_sample_plan(uint32_t nbricks, uint32_t* hist, uint32_t* done)
+BrickSample brick_sample_plan(const BrickLaunch& L, uint32_t* hist)
 {
+  const uint32_t nbricks = L.g.nbricks;
   BrickSample s;
-  s.hist = hist, s.done = done;
+  s.hist = hist, s.total = L.sample_total;
   // stride - 1 a power of two (the order's arithmetic); ~256 sample bricks where possible (a
   // 512^3 field: every 33rd brick, 4 M codes -- the book's bits +0.001 % against every 17th, and
   // pass 1 adds half the sample atomics: -6 us)
@@ -3152,7 +3187,7 @@ int brick_configure(BrickLaunch& L, int elem_bytes, int device)
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu < 1) ncu = 256;
   L.ncu = ncu;
   int per_scan = 0, per_pack = 0;
-  const size_t lds_scan = (size_t)(1 + kBrickWaves * kHistCopies) * kMaxBklen * 4;
+  const size_t lds_scan = (size_t)(1 + kBrickWaves * kHistCopies) * kMaxBklen * 4 + sizeof(SamplePub);
   const size_t lds_pack = 0;  // static LDS only
   hipError_t e1, e2;
   if (elem_bytes == 8) {
@@ -3170,6 +3205,19 @@ int brick_configure(BrickLaunch& L, int elem_bytes, int device)
   L.grid_pack = need < per_pack * ncu ? need : per_pack * ncu;
   if (L.grid_scan < 1) L.grid_scan = 1;
   if (L.grid_pack < 1) L.grid_pack = 1;
+  // the codebook sample's element count (finish_unit validates the completed sample against it):
+  // pass 1 counts the rows of a brick that lie inside the field, whole in x
+  L.sample_total = 0;
+  if (L.g.ndim == 3) {
+    const BrickGeom& g = L.g;
+    const BrickSample s = brick_sample_plan(L, nullptr);
+    uint64_t rows = 0;
+    for (uint32_t j = 0; j < s.count; j++) {
+      const uint32_t t = (s.stride <= 1 ? j : j * s.stride + s.stride / 2) / g.nbx, by = t % g.nby, bz = t / g.nby;
+      rows += (uint64_t)std::min(8u, L.ly - by * 8) * std::min(8u, L.lz - bz * 8);
+    }
+    L.sample_total = (uint32_t)(rows * (uint64_t)g.W);  // < 2^32: the field is
+  }
   return (int)hipSuccess;
 }
 
@@ -3196,11 +3244,12 @@ int launch_brick_scan(const BrickLaunch& L, const T* in, double eb, int radius, 
 #undef SCAN1
     return (int)hipGetLastError();
   }
+  const size_t lds3 = lds + sizeof(SamplePub);
   if (zz)
-    k_brick3_scan<T, 4, true><<<grid, 64 * kBrickWaves, lds, st>>>(in, L.lx, L.ly, L.lz, ebx2_r, r, ol, hist, bhist,
+    k_brick3_scan<T, 4, true><<<grid, 64 * kBrickWaves, lds3, st>>>(in, L.lx, L.ly, L.lz, ebx2_r, r, ol, hist, bhist,
                                                                    bcodes, bklen, g.nbx, g.nby, g.nbricks, pub, sample);
   else
-    k_brick3_scan<T, 4, false><<<grid, 64 * kBrickWaves, lds, st>>>(in, L.lx, L.ly, L.lz, ebx2_r, r, ol, hist, bhist,
+    k_brick3_scan<T, 4, false><<<grid, 64 * kBrickWaves, lds3, st>>>(in, L.lx, L.ly, L.lz, ebx2_r, r, ol, hist, bhist,
                                                                     bcodes, bklen, g.nbx, g.nby, g.nbricks, pub, sample);
   return (int)hipGetLastError();
 }

@@ -222,30 +222,32 @@ struct BrickLaunch {
   uint32_t lx, ly, lz;
   int grid_scan, grid_pack;  // workgroups of the encode passes (per-device occupancy)
   int ncu;
+  uint32_t sample_total;  // 3-D: elements of the codebook sample's bricks inside the field (BrickSample::total)
 };
 
-// fills ncu and the encode-pass grids for `device`
+// fills ncu, the encode-pass grids for `device` and sample_total
 int brick_configure(BrickLaunch& L, int elem_bytes, int device);
 
 // The codebook sample inside pass 1 (sampled codebook mode): every `stride`-th brick (offset
 // stride / 2) is visited FIRST -- iteration j < count takes sample brick j -- and adds its
-// histogram to hist (u32[bklen], global atomics); then done (a u32) counts it, and the wave that
-// completes the sample publishes it to the host (pub_dst, then *pub_flag = pub_epoch), which
-// builds the codebook while pass 1 goes on.  hist == nullptr: no sample, bricks in index order.
+// histogram to hist (u32[bklen], global atomics); then the word after the bins counts it, and the
+// wave that completes the sample publishes it to the host (pub_dst, then *pub_flag = pub_epoch),
+// which builds the codebook while pass 1 goes on.  hist == nullptr: no sample, bricks in index order.
+// 3-D bricks count relaxed, and the completing wave accepts the sample once its bins sum to total
+// (brick.hip finish_unit); linear bricks count with an agent-scope acq_rel and do not use total.
 // the sample histogram's bins lie a 64-B line apart: the sample bricks finish together (first
 // round of pass 1) and their atomics would otherwise queue on the one or two memory channels of
 // a dense 4 KB array (measured: pass 1 +60 us)
 constexpr int kSampleBinStride = 16;
 struct BrickSample {
-  uint32_t* hist = nullptr;  // u32[kMaxBklen * kSampleBinStride]
-  uint32_t* done = nullptr;
+  uint32_t* hist = nullptr;  // u32[kMaxBklen * kSampleBinStride + 1]: the bins, then the count of finished sample bricks
   uint32_t stride = 1, count = 0;
+  uint32_t total = 0;            // 3-D: elements of the sample bricks inside the field (BrickLaunch::sample_total)
   uint32_t* pub_dst = nullptr;   // host-mapped u32[bklen]
   uint32_t* pub_flag = nullptr;  // host-mapped
   uint32_t pub_epoch = 0;
-  int bklen = 0;
 };
-BrickSample brick_sample_plan(uint32_t nbricks, uint32_t* hist, uint32_t* done);
+BrickSample brick_sample_plan(const BrickLaunch& L, uint32_t* hist);
 
 
 // Quant codes between the two encode passes, in brick order (row r of brick b at (64 b + r) W).

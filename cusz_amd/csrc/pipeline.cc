@@ -550,9 +550,8 @@ struct Pipeline {
         // d_shist and hands the completed sample to the host, which builds the codebook (the
         // two-queue book of sample + 1) while pass 1 goes on; the encode launches wait behind
         // the device-polled gate as in the exact mode, but the book is ready long before
-        sample = brick_sample_plan(bl.g.nbricks, d_shist, d_shist + (size_t)kMaxBklen * kSampleBinStride);
+        sample = brick_sample_plan(bl, d_shist);
         sample.pub_dst = h_hist(), sample.pub_flag = const_cast<uint32_t*>(flag(2)), sample.pub_epoch = ++epoch;
-        sample.bklen = bklen;
         pend.side_book = true;  // (the sample's epoch is pend.hist_epoch)
       }
       if (pub_hist && !pend.side_book)  // (2-D bricks: the full histogram, as in the exact mode)
