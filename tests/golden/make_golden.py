@@ -20,16 +20,29 @@ Fixtures written (data only -- inputs and expected outputs):
 * ref_hist.npz      -- codes and the reference serial histogram (hist_generic.seq.cc:17-30).
 * ref_ragged.npz    -- the compiled reference CPU Lorenzo-3D, plain and ZigZag, on a ragged
                        40x24x17 integer field at eb=0.5 where most points are outliers.
+* ref_brick3d.npz, ref_brick3d_b.npz
+                    -- the compiled reference on shapes that take the brick layout (256x16x16,
+                       512x8x24; whole 8^3 tiles, see above): the "exact" lattice field of
+                       tests/edge_fields.py (integers at eb=0.5 with deltas on the outlier
+                       predicate and the code extremes, at the kernels' seams), its codes and
+                       outlier cells for plain f32 and ZigZag f32 (zz_*), and for the first
+                       shape the f64 instantiation on the same field as doubles (f64_*).
+                       Written as .npz with LZMA members (np.load reads them as any other): the
+                       walk's codes are dense, deflate would leave the files larger than the rest.
 """
 import os
 import re
 import sys
+import zipfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT)
+import edge_fields  # noqa: E402
 import pyoracle  # noqa: E402
 
 REF = os.environ.get("PSZ_REFERENCE", "/root/reference")
@@ -53,6 +66,16 @@ def skewed_hist(rng, n_sym, total, width):
     np.add.at(h, c, 1)
     h[0] = rng.integers(0, 50)
     return h
+
+
+def savez_lzma(path, **arrays):
+    """np.savez_compressed with LZMA instead of deflate, and fixed member dates (same bytes each run)."""
+    with zipfile.ZipFile(path, "w") as zf:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_LZMA
+            with zf.open(info, "w", force_zip64=False) as f:
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
 
 
 def main():
@@ -129,6 +152,20 @@ def main():
         codes, ov, oi = fn(rdata, rdims, 0.5)
         out.update({tag + "codes": codes, tag + "ol_val": ov, tag + "ol_idx": oi})
     np.savez_compressed(os.path.join(HERE, "ref_ragged.npz"), **out)
+    # brick-layout shapes (the field has its own generator, seeded from the shape: the fixtures
+    # above stay as they were)
+    for name, bdims, with_f64 in (("ref_brick3d.npz", (256, 16, 16), True), ("ref_brick3d_b.npz", (512, 8, 24), False)):
+        bdata = edge_fields.lattice_field(bdims, np.float32, "exact")
+        out = {"data": bdata, "dims": np.array(bdims)}
+        runs = [("", pyoracle.ref_lorenzo_c_f32, bdata), ("zz_", pyoracle.ref_lorenzo_c_zz_f32, bdata)]
+        if with_f64:
+            bdata64 = edge_fields.lattice_field(bdims, np.float64, "exact")
+            assert np.array_equal(bdata64, bdata)  # the same integers: stored once
+            runs.append(("f64_", pyoracle.ref_lorenzo3d_f64, bdata64))
+        for tag, fn, d in runs:
+            codes, ov, oi = fn(d, bdims, 0.5)
+            out.update({tag + "codes": codes, tag + "ol_val": ov, tag + "ol_idx": oi})
+        savez_lzma(os.path.join(HERE, name), **out)
     print("fixtures written to", HERE)
 
 

@@ -1,7 +1,9 @@
 """The GPU path against fixtures produced by the compiled reference itself (tests/golden,
 make_golden.py): Lorenzo-3D f32, its ZigZag instantiation (lrz.seq.cc:82) and the 3-D template
 for double, integer data at eb = 0.5 (where the reference CPU path and the GPU semantics
-coincide).  Also the HACC-like outlier stress of SURVEY §8d config 3."""
+coincide); on 40x24x16 (the reference layout) and, with the lattice field of
+edge_fields.py, on 256x16x16 and 512x8x24 (the brick layout, two-pass and single-pass).  Also the
+HACC-like outlier stress of SURVEY §8d config 3."""
 import os
 
 import numpy as np
@@ -16,26 +18,39 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.mark.parametrize("fixture,zigzag", [("ref_lrz3d.npz", False), ("ref_lrz3d_zz.npz", True),
-                                            ("ref_lrz3d_f64.npz", False)])
-def test_gpu_matches_reference_fixture(fixture, zigzag):
+# the brick-layout fixtures hold several runs of one field: plain f32 (""), ZigZag f32 ("zz_") and,
+# in the first, the f64 instantiation ("f64_"); each in the default and the single-pass codebook mode
+BRICK_FIXTURES = [pytest.param(f, tag == "zz_", tag, mode, id=f"{f}-{tag or 'plain'}{mid}")
+                  for f, tags in (("ref_brick3d.npz", ("", "zz_", "f64_")), ("ref_brick3d_b.npz", ("", "zz_")))
+                  for tag in tags
+                  for mode, mid in ((cz.CODEBOOK_SAMPLED, "-sampled"), (cz.CODEBOOK_STREAM, "-stream"))]
+
+
+@pytest.mark.parametrize("fixture,zigzag,tag,mode", [
+    pytest.param("ref_lrz3d.npz", False, "", None, id="ref_lrz3d.npz-False"),
+    pytest.param("ref_lrz3d_zz.npz", True, "", None, id="ref_lrz3d_zz.npz-True"),
+    pytest.param("ref_lrz3d_f64.npz", False, "", None, id="ref_lrz3d_f64.npz-False")] + BRICK_FIXTURES)
+def test_gpu_matches_reference_fixture(fixture, zigzag, tag, mode):
     g = np.load(os.path.join(GOLDEN, fixture))
     dims = tuple(int(v) for v in g["dims"])
-    data = g["data"]
+    data = g["data"].astype(np.float64) if tag == "f64_" else g["data"]
     f64 = data.dtype == np.float64
     r = cz.Resource(cz.F8 if f64 else cz.F4, dims, cz.LorenzoZigZag if zigzag else cz.Lorenzo)
+    if mode is not None:
+        r.set_codebook(mode)
     d = to_device(data)
     ptr, nb, _ = r.compress(d.data_ptr(), 0.5)
+    assert r.internals().layout == (cz.LAYOUT_REFERENCE if mode is None else cz.LAYOUT_BRICK)
     arch = d2h(ptr, nb).tobytes()
     r.decode_codes(ptr)
     sync()
     codes = d2h(r.internals().d_quant_codes, 2 * data.size, np.uint16)
-    np.testing.assert_array_equal(codes, g["codes"])
+    np.testing.assert_array_equal(codes, g[tag + "codes"])
     a = parse_archive(arch)
     order = np.argsort(a["ol_idx"], kind="stable")
-    ref_order = np.argsort(g["ol_idx"], kind="stable")
-    np.testing.assert_array_equal(a["ol_idx"][order], g["ol_idx"][ref_order])
-    np.testing.assert_array_equal(a["ol_val"][order], g["ol_val"][ref_order])
+    ref_order = np.argsort(g[tag + "ol_idx"], kind="stable")
+    np.testing.assert_array_equal(a["ol_idx"][order], g[tag + "ol_idx"][ref_order])
+    np.testing.assert_array_equal(a["ol_val"][order], g[tag + "ol_val"][ref_order])
     out = torch.full((data.size,), float("nan"), dtype=torch.float64 if f64 else torch.float32, device="cuda")
     r.decompress(ptr, nb, out.data_ptr())
     sync()

@@ -47,6 +47,12 @@ def test_sampled_parity(oracle, dims, dtype, eb, zz, radius, kind, mode):
         data = datagen.smooth3d_np(dims, sum(dims), dtype=dtype)
     else:
         data = np.random.default_rng(sum(dims)).standard_normal(n).astype(dtype)
+    sampled_roundtrip(oracle, data, dims, dtype, eb, zz, radius, mode)
+
+
+def sampled_roundtrip(oracle, data, dims, dtype, eb, zz, radius, mode):
+    """The parity contract above for one field on a 3-D brick layout -> the archive's bytes."""
+    n = int(np.prod(dims))
     r = cz.Resource(cz.F4 if dtype == np.float32 else cz.F8, dims, cz.LorenzoZigZag if zz else cz.Lorenzo)
     r.set_codebook(mode)
     d_in = to_device(data)
@@ -94,6 +100,7 @@ def test_sampled_parity(oracle, dims, dtype, eb, zz, radius, kind, mode):
     bad = np.flatnonzero(out.cpu().numpy().view(ubits) != xo.view(ubits))
     assert bad.size == 0, f"{bad.size} reconstruction mismatches"
     r.close()
+    return arch
 
 
 @pytest.mark.parametrize("mode", [cz.CODEBOOK_SAMPLED, cz.CODEBOOK_STREAM], ids=["sampled", "stream"])

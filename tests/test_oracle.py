@@ -71,6 +71,35 @@ def test_ref_lorenzo3d_zigzag_f64_crosscheck(oracle, fixture, zigzag):
     np.testing.assert_array_equal(out, g["data"])
 
 
+@pytest.mark.parametrize("fixture,tag", [("ref_brick3d.npz", ""), ("ref_brick3d.npz", "zz_"), ("ref_brick3d.npz", "f64_"),
+                                         ("ref_brick3d_b.npz", ""), ("ref_brick3d_b.npz", "zz_")])
+def test_ref_brick_layout_fixtures(oracle, fixture, tag):
+    """Compiled reference on shapes that take the brick layout (256x16x16, 512x8x24), on the "exact"
+    lattice field: deltas on the outlier predicate and the code extremes at the kernels' seams."""
+    import edge_fields as ef
+    from oracle import pyoracle
+
+    g = np.load(os.path.join(GOLDEN, fixture))
+    dims = tuple(int(v) for v in g["dims"])
+    zigzag, dtype = tag == "zz_", np.float64 if tag == "f64_" else np.float32
+    data = g["data"].astype(dtype)
+    # the field is the generator's (the GPU lattice tests run what the fixture pins)
+    np.testing.assert_array_equal(data, ef.lattice_field(dims, dtype, "exact"))
+    ref = g[tag + "codes"], g[tag + "ol_val"], g[tag + "ol_idx"]
+    if pyoracle.ref_available():  # the reference built here gives what the fixture recorded
+        fn = {"": pyoracle.ref_lorenzo_c_f32, "zz_": pyoracle.ref_lorenzo_c_zz_f32, "f64_": pyoracle.ref_lorenzo3d_f64}[tag]
+        for live, stored in zip(fn(data, dims, 0.5), ref):
+            np.testing.assert_array_equal(live, stored)
+    codes, ov, oi = oracle.lorenzo_c(data, dims, eb=0.5, zigzag=zigzag)
+    np.testing.assert_array_equal(codes, ref[0])
+    order = np.argsort(ref[2], kind="stable")
+    np.testing.assert_array_equal(oi, ref[2][order])
+    np.testing.assert_array_equal(ov, ref[1][order])
+    assert len(oi) > 100 and codes.max() == (2 * R - 2 if zigzag else 2 * R - 1)
+    out = oracle.lorenzo_x(codes, ov, oi, dims, eb=0.5, zigzag=zigzag, dtype=dtype)
+    np.testing.assert_array_equal(out, data)
+
+
 @pytest.mark.parametrize("zigzag", [False, True])
 def test_ref_ragged_dense_outliers(oracle, zigzag):
     """The compiled reference on a ragged field where almost every point is an outlier: its
