@@ -1,5 +1,5 @@
 // cusz_amd/csrc/archive_device.hh -- device-side archive header fill, shared by the finalize
-// kernel (pipeline_kernels.hip) and the brick reservation kernel (brick.hip).
+// kernel (pipeline_kernels.hip) and the brick plan and single-pass finish kernels (brick_pack.hip, brick_stream.hip).
 //
 // Layouts: psz_header psz/include/cusz/header.h:19-48 (entry[6] @56, splen @104), phf_header
 // codec/hf/include/hf.h:40-46 (total_nbit @24, total_ncell @32, entry[6] @40).

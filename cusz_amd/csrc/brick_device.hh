@@ -1,0 +1,179 @@
+// cusz_amd/csrc/brick_device.hh -- what the fused brick kernels for gfx950 share across their
+// translation units (brick_scan.hip, brick_pack.hip, brick_decode.hip, brick_stream.hip).  In the
+// brick pipeline the Lorenzo predictor feeds the Huffman packer (compress) and the Huffman decoder
+// feeds the Lorenzo reconstructor directly (decompress).
+//
+// Reference semantics (unchanged, bit-exact): predictor lrz_c.cuhip.inl:275-372 (3D 8^3 tiles),
+// reconstruct lrz_x.cuhip.inl:271-360, histogram hist.cuhip.inl:55-89, chunked MSB-first
+// Huffman cells hf_kernels.cuhip.inl:97-157, canonical decode hf_kernels.cuhip.inl:331-396.
+//
+// MI355X layout.  A wave owns a brick of W x 8 x 8 elements (W = 64 V: lane l holds x in
+// [l V, l V + V)).  The Huffman chunk length is W, so every brick ROW (fixed y, z) is exactly one
+// reference chunk: chunk c covers codes [c W, c W + W) of the linear (x-fastest) order.
+//   pass 1 (brick_scan.hip, k_brick3_scan):  predict -> codes in brick order (byte rows; u16 rows
+//                            when a code leaves the byte window, one mask bit per row), per-unit
+//                            histogram (u16, kept for the plan), global histogram, outlier slots.
+//                            Reads the input once.
+//   host:                    canonical codebook from the global histogram (exact reference heap).
+//   plan (brick_pack.hip, k_brick_plan):  a unit's bits = sum(hist_u[s] * len[s]); its region in
+//                            the bitstream is that many bits plus one partial cell per row -- an
+//                            upper bound, known BEFORE encoding, so every unit writes at a fixed
+//                            offset: no look-back, no scratch, no gather.  The last block writes
+//                            the headers.
+//   pass 2 (brick_pack.hip, k_brick3_pack):  codes (read back, not re-predicted) -> codewords ->
+//                            pack each row (= chunk) into LDS cells -> store at region + running
+//                            offset; par_nbit / par_entry; the unit's outlier slot is copied out.
+//   decompress (brick_decode.hip, k_brick3_decode): one wave per brick, one chunk per lane decoded
+//                            in x-blocks of 32 symbols (f32; 64 for f64) into an LDS code tile; the
+//                            block is reconstructed (reference scan order) and stored as whole rows.
+// Single-pass mode (brick_stream.hip: k_brick3_sample, k_brick3_stream, k_brick3_stream_finish):
+// the book comes from a 1/16 sample of 32 x 8 x 8 units before the field is predicted, and one
+// pass -- a workgroup per brick, a wave per y-step -- predicts, sizes (look-back over the bricks)
+// and packs each brick.
+// The archive is the reference phf format: par_entry[c] points at chunk c (the reference decoder
+// reads chunk c from there, hf_kernels.cuhip.inl:386-391); chunks are laid out brick by brick,
+// and the few cells between a brick's last chunk and the next region are zero.
+//
+// Everything here has internal linkage or is __forceinline__: each .hip file compiles its own copy.
+#pragma once
+
+#include <algorithm>
+#include <type_traits>
+
+#include "archive_device.hh"
+#include "common.hh"
+#include "hf_device.hh"
+#include "kernels.hh"
+#include "lrz_device.hh"
+#include "pub_device.hh"
+
+namespace cusz_amd {
+
+using namespace lrzd;
+
+namespace {
+
+constexpr int kBrickWaves = 4;  // waves per workgroup in the encode passes
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t kBufRsrcW3 = 0x00020000;  // raw buffer resource word 3 (gfx9)
+constexpr uint32_t kOOB = 0x80000000u;       // buffer offset past any range: the load returns 0
+// A unit = kUnitBricks consecutive bricks, processed by one wave in both encode passes: one
+// histogram record (u16 counts: a unit has at most 32768 elements), one outlier slot and one
+// reserved bitstream region per unit.
+constexpr int kUnitBricks = 1;
+
+__device__ __forceinline__ uint32_t readlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+
+// cache-policy bits of the encoders' field loads: 2 = nontemporal
+// (config 2 pass 1 189 -> 163 us: the streamed field no longer evicts the code rows pass 2 reads)
+constexpr int kScanLoadAux = 2;
+
+// The rows of a brick, for the encoders that stream the field brick by brick (pass 1 and the
+// single-pass encoder): raw buffer loads from the brick's origin, issued ahead of their use and
+// across brick boundaries.
+template <typename T, int V>
+struct StepLoader {
+  const T* in;
+  size_t plane;
+  uint32_t lx, ly, lz, nbx, nby, nbricks;
+  int reverse;
+  uint32_t lane;
+  __device__ __forceinline__ uint32_t brick_of(uint32_t it) const { return reverse ? nbricks - 1 - it : it; }
+  // Rows (y, z = 0..7) of brick `it` by raw buffer loads from the brick's origin: one 16-B (f64:
+  // two) load per lane and row, rows outside the field get an offset past the range and read 0.
+  // Straight-line code: no per-row branches, so the waitcnt pass can count the loads exactly.
+  // row `row` = 8 y + z of brick `it` (rows outside the field read 0)
+  __device__ __forceinline__ void issue_row(uint32_t it, int row, T (&dst)[V]) const
+  {
+    // past the last brick the load still issues (at brick 0's origin, past the range: reads 0,
+    // touches no memory): every path issues the same loads, so the compiler counts the waits
+    // (vmcnt(7) for the row loaded 8 rows ago, not vmcnt(0): compress -3 us, 1-D -9 us)
+    const bool live = it < nbricks;
+    const uint32_t b = live ? brick_of(it) : 0u, bx = b % nbx, t = b / nbx, by = t % nby, bz = t / nby;
+    const T* origin = in + (size_t)bz * 8 * plane + (size_t)by * 8 * lx + (size_t)bx * (64 * V);
+    const uint32_t span = (uint32_t)(8 * plane * sizeof(T));  // < 2^31 (brick_geom)
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(origin), 0, (int)span, (int)kBufRsrcW3);
+    const uint32_t y = (uint32_t)row >> 3, z = (uint32_t)row & 7u;
+    const bool ok = live && by * 8 + y < ly && bz * 8 + z < lz;
+    const uint32_t off =
+        ok ? (uint32_t)(((size_t)z * plane + (size_t)y * lx) * sizeof(T)) + lane * (V * sizeof(T)) : span;
+#pragma unroll
+    for (int h = 0; h < (int)(V * sizeof(T) / 16); h++) {
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off + 16 * h), 0, kScanLoadAux);
+      __builtin_memcpy(reinterpret_cast<char*>(&dst[0]) + 16 * h, &v, 16);
+    }
+  }
+  // The same loads with the brick's address work done once per brick (BrickRows): per row only
+  // the in-brick offset and two compares, instead of the brick coordinates, the 64-bit origin and
+  // the descriptor again for every row (pass 1: ~50 scalar instructions and the SGPR spills they
+  // cause, per row).
+  struct BrickRows {
+    __amdgpu_buffer_rsrc_t rs;  // at the brick's origin, 8 planes long
+    uint32_t nyv, nzv;          // rows y < nyv, z < nzv lie in the field (0: past the last brick)
+  };
+  __device__ __forceinline__ BrickRows rows_of(uint32_t it) const
+  {
+    const bool live = it < nbricks;
+    const uint32_t b = live ? brick_of(it) : 0u, bx = b % nbx, t = b / nbx, by = t % nby, bz = t / nby;
+    const T* origin = in + (size_t)bz * 8 * plane + (size_t)by * 8 * lx + (size_t)bx * (64 * V);
+    const uint32_t span = (uint32_t)(8 * plane * sizeof(T));  // < 2^31 (brick_geom)
+    return {__builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(origin), 0, (int)span, (int)kBufRsrcW3),
+            live ? min(8u, ly - by * 8) : 0u, live ? min(8u, lz - bz * 8) : 0u};
+  }
+  __device__ __forceinline__ void issue_row(const BrickRows& br, uint32_t y, uint32_t z, T (&dst)[V]) const
+  {
+    const uint32_t span = (uint32_t)(8 * plane * sizeof(T));
+    const bool ok = y < br.nyv && z < br.nzv;
+    const uint32_t off = ok ? (z * (uint32_t)plane + y * lx) * (uint32_t)sizeof(T) + lane * (V * sizeof(T)) : span;
+#pragma unroll
+    for (int h = 0; h < (int)(V * sizeof(T) / 16); h++) {
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(br.rs, (int)(off + 16 * h), 0, kScanLoadAux);
+      __builtin_memcpy(reinterpret_cast<char*>(&dst[0]) + 16 * h, &v, 16);
+    }
+  }
+};
+
+// Row packing (hfd::pack4_or_lj / hfd::pack_words into a wave's LDS cells), pass 2 and the
+// single-pass encoder:
+constexpr int kPackRowMax = (64 * 4 * kLmax + 31) / 32 + 2;  // words one row's packing may touch
+
+// four consecutive elements (16 B for f32, 32 B for f64) to / from 16-B aligned LDS
+template <typename T>
+__device__ __forceinline__ void lds_store4(T* p, const T (&v)[4])
+{
+#pragma unroll
+  for (int i = 0; i < (int)sizeof(T) / 4; i++) {
+    u32x4 w;
+    __builtin_memcpy(&w, reinterpret_cast<const char*>(&v[0]) + 16 * i, 16);
+    reinterpret_cast<u32x4*>(p)[i] = w;
+  }
+}
+template <typename T>
+__device__ __forceinline__ void lds_load4(const T* p, T (&v)[4])
+{
+#pragma unroll
+  for (int i = 0; i < (int)sizeof(T) / 4; i++) {
+    const u32x4 w = reinterpret_cast<const u32x4*>(p)[i];
+    __builtin_memcpy(reinterpret_cast<char*>(&v[0]) + 16 * i, &w, 16);
+  }
+}
+
+}  // namespace
+
+// blocks of pass 2 (k_brick3_pack, brick_pack.hip) resident per CU, 0 when the query fails: for
+// brick_configure (brick_scan.hip), which sizes both encode grids
+int brick_pack_blocks_per_cu();
+
+// Diagnostic build (make prof, psz_amd_debug_brick_profile): the decoders and the single-pass
+// encoder sum per-phase clocks and counts over their waves into 16 counters.  A __device__ array
+// is private to its translation unit, so brick_decode.hip and brick_stream.hip keep one each;
+// psz_amd_debug_brick_profile (brick_decode.hip) returns their sum and resets both.
+#ifdef CUSZ_AMD_DEC_PROFILE
+#define BPROF(...) __VA_ARGS__
+// adds brick_stream.hip's counters to host[0..15]; clears them when `reset`
+int brick_stream_profile(unsigned long long* host, int reset);
+#else
+#define BPROF(...)
+#endif
+
+}  // namespace cusz_amd

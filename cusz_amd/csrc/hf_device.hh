@@ -1,5 +1,5 @@
 // cusz_amd/csrc/hf_device.hh -- device helpers shared by the Huffman kernels (huffman.hip)
-// and the fused brick kernels (brick.hip): wave64 scans, MSB-first codeword packing into LDS
+// and the fused brick kernels (brick_*.hip): wave64 scans, MSB-first codeword packing into LDS
 // cells, and the canonical-code decode table.
 //
 // Canonical decoding follows the reference rule (codec/hf/src/hf_kernels.cuhip.inl:351-365):
@@ -115,20 +115,6 @@ __device__ __forceinline__ void pack4_or_lj(uint32_t* cells, uint32_t pos, const
   atomicOr(&c[2], __builtin_amdgcn_alignbit(lo, 0u, pos & 31u));
 }
 
-// ---- decode tables --------------------------------------------------------------------------
-// Entry (u32) for the codeword(s) at the top of a window: [9:0] first symbol, [15:14] symbols
-// (1 or 2), [25:16] second symbol, [30:26] bits consumed, [31] two symbols.  0 = not in this
-// table -- and, read as an entry, "0 symbols, 0 bits": a decoder may step on it without moving.
-// The symbols sit where one 32-bit LDS store writes them as two consecutive u16 codes
-// (value & 0x03FF03FF).
-__device__ __forceinline__ uint32_t ent_pack(uint32_t two, uint32_t bits, uint32_t s0, uint32_t s1)
-{
-  return (two << 31) | (bits << 26) | (s1 << 16) | ((1u + two) << 14) | s0;
-}
-__device__ __forceinline__ uint32_t ent_bits(uint32_t e) { return (e >> 26) & 31u; }
-__device__ __forceinline__ uint32_t ent_nsym(uint32_t e) { return (e >> 14) & 3u; }
-constexpr uint32_t kEntSymMask = 0x03FF03FFu;
-
 // longest code length present (last l with entry[l+1] > entry[l])
 __device__ __forceinline__ int longest_code(const uint32_t* entry)
 {
@@ -138,211 +124,20 @@ __device__ __forceinline__ int longest_code(const uint32_t* entry)
   return m;
 }
 
-// One symbol from a left-justified 32-bit window by the reference rule.  The thresholds
-// first[l] * 2^(32-l) never increase with l (canonical construction), so the failing lengths
-// form a prefix 1..m and the code length is 1 + the number of failing lengths.
-__device__ __forceinline__ uint32_t tab_decode1(uint32_t v, const uint32_t* first, int maxl, const uint32_t* base,
-                                                const uint16_t* keys, uint32_t bklen, uint32_t& sym)
-{
-  uint32_t l = 1;
-#pragma unroll
-  for (int k = 1; k <= kLmax; k++) l += (k <= maxl && (v >> (32 - k)) < first[k]) ? 1u : 0u;
-  if (l > (uint32_t)maxl) l = (uint32_t)maxl;
-  sym = keys[min(base[l] + (v >> (32 - l)), bklen - 1)];
-  return l;
-}
-
-// Decode tables resident in LDS.
-//  L1: 2^B entries indexed by the next B bits, one or two whole codewords of <= B bits; 0 for
-//      a prefix of a longer code.
-//  L2: single-symbol entries indexed DIRECTLY by the next 16 bits.  Canonical codes put every
-//      code longer than B bits below first[B] (longer codes are numerically smaller), so only
-//      windows whose B-bit prefix is < first[B] have an entry: first[B] << (16 - B) entries
-//      (capped; its last entry and every entry past them stay 0).  Exactly one of the two
-//      lookups is nonzero for a code of <= 16 bits, so entry = L1 | L2 (read together).
-//  Codes longer than 16 bits (or past the cap) count failing lengths against thresholds the
-//  caller keeps in registers (DecRegs).
-constexpr int kL2Bits = 16;
-#ifndef CUSZ_AMD_SLOW_UNROLL
-#define CUSZ_AMD_SLOW_UNROLL 16  // unroll of the rare >16-bit code search (1: keep it small)
-#endif
-#ifndef CUSZ_AMD_DEC_L2CAP
-#define CUSZ_AMD_DEC_L2CAP 4096
-#endif
-constexpr int kL2Cap = CUSZ_AMD_DEC_L2CAP;
-
-template <int B>
-struct LdsTables {
-  uint32_t l1[1 << B];
-  uint32_t l2[kL2Cap];
-  uint32_t first[32];
-  uint32_t base[32];
-  uint32_t entry[32];
-  uint32_t maxl;
-  uint32_t pad[3];
-  uint16_t keys[kMaxBklen];
-};
-
-// wave-uniform thresholds for the rare untabulated codes (first[l], l = 12..27)
-constexpr int kSlowFrom = 12;
-struct DecRegs {
-  uint32_t first[kLmax - kSlowFrom + 1];
-  uint32_t maxl;
-  uint32_t thr;  // windows below thr start with a code longer than B bits (lookup1)
-};
-
-// Cooperative build by the whole workgroup (ends with a barrier).
-template <int B>
-__device__ __forceinline__ void build_tables(LdsTables<B>& t, const uint8_t* revbook, int bklen)
-{
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int32_t* rv = reinterpret_cast<const int32_t*>(revbook);
-  if (tid < 32) t.first[tid] = (uint32_t)rv[tid], t.entry[tid] = (uint32_t)rv[32 + tid];
-  const uint16_t* keys = reinterpret_cast<const uint16_t*>(revbook + 256);
-  for (int i = tid; i < bklen; i += nt) t.keys[i] = keys[i];
-  __syncthreads();
-  const int maxl = longest_code(t.entry);
-  if (tid < 32) {
-    t.base[tid] = t.entry[tid] - t.first[tid];
-    if (tid == 0) t.maxl = (uint32_t)maxl;
-  }
-  __syncthreads();
-  uint32_t first[32];  // registers: the unrolled threshold loop reads no LDS
-#pragma unroll
-  for (int k = 0; k < 32; k++) first[k] = t.first[k];
-  const uint32_t* base = t.base;
-  const uint32_t ub = (uint32_t)bklen;
-  for (uint32_t i = tid; i < (1u << B); i += nt) {
-    const uint32_t v = i << (32 - B);
-    uint32_t s0, s1, e = 0;
-    const uint32_t l0 = tab_decode1(v, first, maxl, base, t.keys, ub, s0);
-    if (l0 <= (uint32_t)B) {
-      const uint32_t rest = B - l0;
-      const uint32_t l1 = rest ? tab_decode1(v << l0, first, maxl, base, t.keys, ub, s1) : 99u;
-      e = l1 <= rest ? ent_pack(1, l0 + l1, s0, s1) : ent_pack(0, l0, s0, 0);
-    }
-    t.l1[i] = e;
-  }
-  const uint32_t P = maxl > B ? min(first[B], 1u << B) : 0u;
-  const uint32_t n2 = min(P << (kL2Bits - B), (uint32_t)kL2Cap - 1);
-  for (uint32_t q = tid; q < (uint32_t)kL2Cap; q += nt) {
-    uint32_t e = 0;
-    if (q < n2) {
-      uint32_t s0;
-      const uint32_t l = tab_decode1(q << (32 - kL2Bits), first, maxl, base, t.keys, ub, s0);
-      if (l <= (uint32_t)kL2Bits) e = ent_pack(0, l, s0, 0);
-    }
-    t.l2[q] = e;
-  }
-  __syncthreads();
-}
-
-template <int B>
-__device__ __forceinline__ DecRegs load_dec_regs(const LdsTables<B>& t)
-{
-  static_assert(B + 1 >= kSlowFrom, "slow path thresholds start at B + 1");
-  DecRegs r;
-#pragma unroll
-  for (int q = 0; q < kLmax - kSlowFrom + 1; q++) r.first[q] = __builtin_amdgcn_readfirstlane(t.first[kSlowFrom + q]);
-  r.maxl = __builtin_amdgcn_readfirstlane(t.maxl);
-  // canonical codes: a code is longer than B bits iff the window's top B bits are < first[B]
-  const uint32_t fb = __builtin_amdgcn_readfirstlane(t.first[B]);
-  r.thr = r.maxl <= (uint32_t)B ? 0u : (fb >= (1u << B) ? 0xFFFFFFFFu : fb << (32 - B));
-  return r;
-}
-
-// Entry for the codeword(s) at the top of `win`.
-template <int B>
-__device__ __forceinline__ uint32_t lookup(const LdsTables<B>& t, const DecRegs& rg, uint32_t win, uint32_t bklen)
-{
-  const uint32_t e1 = t.l1[win >> (32 - B)];
-  const uint32_t e2 = t.l2[min(win >> (32 - kL2Bits), (uint32_t)kL2Cap - 1)];
-  uint32_t e = e1 | e2;
-  if (__builtin_expect(e == 0, 0)) {  // all lengths <= 16 failed: count the rest
-    uint32_t l = B + 1;
-#pragma unroll CUSZ_AMD_SLOW_UNROLL
-    for (int q = B + 1 - kSlowFrom; q < kLmax - kSlowFrom + 1; q++)
-      l += (kSlowFrom + q < (int)rg.maxl && (win >> (32 - (kSlowFrom + q))) < rg.first[q]) ? 1u : 0u;
-    if (l > rg.maxl) l = rg.maxl;
-    const uint32_t s = t.keys[min(t.base[l] + (win >> (32 - l)), bklen - 1)];
-    e = ent_pack(0, l, s, 0);
-  }
-  return e;
-}
-
-// The rare codes longer than 16 bits (no table entry): count the failing lengths against the
-// thresholds in registers.
-template <int B>
-__device__ __forceinline__ uint32_t lookup_long(const LdsTables<B>& t, const DecRegs& rg, uint32_t win, uint32_t bklen)
-{
-  uint32_t l = B + 1;
-#pragma unroll
-  for (int q = B + 1 - kSlowFrom; q < kLmax - kSlowFrom + 1; q++)
-    l += (kSlowFrom + q < (int)rg.maxl && (win >> (32 - (kSlowFrom + q))) < rg.first[q]) ? 1u : 0u;
-  if (l > rg.maxl) l = rg.maxl;
-  const uint32_t s = t.keys[min(t.base[l] + (win >> (32 - l)), bklen - 1)];
-  return ent_pack(0, l, s, 0);
-}
-
-// One table read, no branch: the entry, or 0 for a code longer than 16 bits (lookup_long).
-template <int B>
-__device__ __forceinline__ uint32_t lookup_short(const LdsTables<B>& t, const DecRegs& rg, uint32_t win)
-{
-  const uint32_t a = win < rg.thr ? (1u << B) + min(win >> (32 - kL2Bits), (uint32_t)kL2Cap - 1) : win >> (32 - B);
-  return t.l1[a];
-}
-
-// Same entry as lookup() with ONE table read: L1 and L2 are exclusive (L2 holds exactly the
-// windows below rg.thr), so the window picks its table before the read.  L2 follows L1 in
-// LdsTables, so both are one array.
-template <int B>
-__device__ __forceinline__ uint32_t lookup1(const LdsTables<B>& t, const DecRegs& rg, uint32_t win, uint32_t bklen)
-{
-  static_assert(offsetof(LdsTables<B>, l2) == sizeof(uint32_t) << B, "l2 follows l1");
-  const uint32_t a = win < rg.thr ? (1u << B) + min(win >> (32 - kL2Bits), (uint32_t)kL2Cap - 1) : win >> (32 - B);
-  uint32_t e = t.l1[a];
-  if (__builtin_expect(e == 0, 0)) {  // all lengths <= 16 failed: count the rest
-    uint32_t l = B + 1;
-#pragma unroll
-    for (int q = B + 1 - kSlowFrom; q < kLmax - kSlowFrom + 1; q++)
-      l += (kSlowFrom + q < (int)rg.maxl && (win >> (32 - (kSlowFrom + q))) < rg.first[q]) ? 1u : 0u;
-    if (l > rg.maxl) l = rg.maxl;
-    const uint32_t s = t.keys[min(t.base[l] + (win >> (32 - l)), bklen - 1)];
-    e = ent_pack(0, l, s, 0);
-  }
-  return e;
-}
-
-// Same entry as lookup(), reading the L2 table only for the lanes whose L1 entry is 0 (a second,
-// dependent LDS round trip for them instead of an L2 read by every lane on every step).
-template <int B>
-__device__ __forceinline__ uint32_t lookup_l1_first(const LdsTables<B>& t, const DecRegs& rg, uint32_t win,
-                                                    uint32_t bklen)
-{
-  uint32_t e = t.l1[win >> (32 - B)];
-  if (e == 0) {
-    e = t.l2[min(win >> (32 - kL2Bits), (uint32_t)kL2Cap - 1)];
-    if (__builtin_expect(e == 0, 0)) {
-      uint32_t l = B + 1;
-#pragma unroll CUSZ_AMD_SLOW_UNROLL
-      for (int q = B + 1 - kSlowFrom; q < kLmax - kSlowFrom + 1; q++)
-        l += (kSlowFrom + q < (int)rg.maxl && (win >> (32 - (kSlowFrom + q))) < rg.first[q]) ? 1u : 0u;
-      if (l > rg.maxl) l = rg.maxl;
-      const uint32_t s = t.keys[min(t.base[l] + (win >> (32 - l)), bklen - 1)];
-      e = ent_pack(0, l, s, 0);
-    }
-  }
-  return e;
-}
-
-// ---- compact decode tables (the 3-D fused decoder) ---------------------------------------------
+// ---- decode tables (the fused decoders, brick_decode.hip) ---------------------------------------
 // One u32 entry per window, laid out for few instructions per decode step:
 //   [9:0] first symbol, [12:10] 2 x symbols (0, 2 or 4: the tile pointer's advance in bytes),
 //   [25:16] second symbol, [31:27] bits consumed; 0 = "no symbol, no bits" (a code longer than
-//   16 bits, or a window past the L2 cap: decoded by lookup_long).
-// L1 (2^12 entries) by the top 12 bits, one or two whole codewords; L2 (kL2Cap4 entries) right
-// after it, by the top 16 bits, for the windows below the canonical threshold first[12] << 20.
+//   16 bits, or a window past the L2 cap: decoded by lookup_long4) -- a decoder may step on it
+//   without moving.
+// L1 (2^12 entries) by the top 12 bits, one or two whole codewords; 0 for a prefix of a longer
+// code.  L2 (kL2Cap4 entries) right after it, single-symbol entries indexed directly by the top
+// kL2Bits = 16 bits.  Canonical codes put every code longer than 12 bits below first[12] (longer
+// codes are numerically smaller), so only the windows below the canonical threshold
+// first[12] << 20 have an L2 entry (capped; the last entry and every window past the cap stay 0),
+// and a window picks its table before the read.
 // Stored symbols are (e & kEnt4SymMask): two u16 halves.
+constexpr int kL2Bits = 16;
 constexpr int kL2Cap4 = 2048;
 constexpr uint32_t kEnt4SymMask = 0x03FF03FFu;
 __device__ __forceinline__ uint32_t ent4_pack(uint32_t nsym, uint32_t bits, uint32_t s0, uint32_t s1)
@@ -362,8 +157,8 @@ struct Tab4 {
   uint16_t keys[kMaxBklen];
 };
 
-// Cooperative build by the whole workgroup (ends with a barrier); same decoding rule as
-// build_tables (hf_kernels.cuhip.inl:351-365), entries in the compact format.  Every decoder
+// Cooperative build by the whole workgroup (ends with a barrier), by the reference's decoding
+// rule (hf_kernels.cuhip.inl:351-365).  Every decoder
 // workgroup builds it before its first step, so it is kept cheap (≈ 2x fewer VALU than one
 // counting decode per symbol slot):
 //  * the failing-length count compares (win >> 1) with uniform thresholds first[k] << (31 - k)

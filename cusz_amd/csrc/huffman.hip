@@ -25,61 +25,6 @@ namespace cusz_amd {
 
 namespace {
 
-
-// inclusive wave64 prefix sum with DPP (row_shr inside 16-lane rows, then row_bcast15/31 across
-// rows): six VALU ops instead of six LDS-routed ds_bpermute round trips
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int /*lane*/)
-{
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31
-  return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-
-
-// Pack this thread's codewords (MSB-first, starting at bit `pos` of the chunk) into the LDS
-// cell buffer.  Words that only this thread touches are plain stores; the first word (when
-// `pos` is not word aligned) and the trailing partial word may be shared with neighbouring
-// threads and are merged with LDS atomic OR (the buffer is zeroed beforehand).
-template <int N>
-__device__ __forceinline__ void pack_words(uint32_t* cells, uint32_t pos, const uint32_t (&w)[N], int mine)
-{
-  uint32_t q = pos >> 5;
-  uint64_t acc = 0;
-  uint32_t fill = pos & 31;  // bits already owned by earlier threads in word q
-  bool first = fill != 0;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    if (i >= mine) break;
-    const uint32_t l = w[i] >> 27, v = w[i] & 0x07FFFFFFu;
-    acc |= (uint64_t)v << (64 - fill - l);
-    fill += l;
-    if (fill >= 32) {
-      const uint32_t word = (uint32_t)(acc >> 32);
-      if (first)
-        atomicOr(&cells[q], word);
-      else
-        cells[q] = word;
-      first = false;
-      acc <<= 32;
-      fill -= 32;
-      q++;
-    }
-  }
-  if (fill) atomicOr(&cells[q], (uint32_t)(acc >> 32));
-}
-
 // codes are read 16 per lane per round (two 16-B loads, issued for the next round before the
 // current one is packed)
 constexpr int kEncW = 4;    // chunks (waves) per workgroup
@@ -167,7 +112,7 @@ __global__ void __launch_bounds__(64 * kPackWaves) k_hf_pack(HfEncodeArgs a, int
         w[i] = i < mine ? s_book[code] : 0u;
         bits += w[i] >> 27;
       }
-      const uint32_t inc = wave_incl_scan(bits, lane);
+      const uint32_t inc = hfd::wave_incl_scan(bits);
       // full rounds whose 4-code groups each fit 64 bits (every lane): Horner-pack each group and
       // OR it in (hf_device.hh pack4_or); otherwise the general word-by-word packer
       uint32_t lg[kRound / 4];
@@ -187,7 +132,7 @@ __global__ void __launch_bounds__(64 * kPackWaves) k_hf_pack(HfEncodeArgs a, int
         }
       }
       else if (mine)
-        pack_words<kRound>(cells, nbits + inc - bits, w, mine);
+        hfd::pack_words<kRound>(cells, nbits + inc - bits, w, mine);
       nbits += __shfl(inc, 63);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -222,8 +167,8 @@ __global__ void __launch_bounds__(256) k_hf_tile_sums(const uint32_t* __restrict
       acc += (nb + 31) >> 5;
       bits += nb;  // a tile of 64 chunks of <= 8192 codes of <= 27 bits: < 2^32
     }
-    acc = wave_sum(acc);
-    bits = wave_sum(bits);
+    acc = hfd::wave_sum(acc);
+    bits = hfd::wave_sum(bits);
     if (lane == 0) {  // (agent scope: the last workgroup may read them from another XCD)
       __hip_atomic_store(tile_sum + t, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(tile_bits + t, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -243,7 +188,7 @@ __global__ void __launch_bounds__(256) k_hf_tile_sums(const uint32_t* __restrict
       tb += i < ntiles ? __hip_atomic_load(tile_bits + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
       sum += v[k];
     }
-    const uint32_t inc = wave_incl_scan(sum, lane);
+    const uint32_t inc = hfd::wave_incl_scan(sum);
     if (lane == 63) s_wc[wid] = inc;
     __syncthreads();
     uint32_t run = carry, tot = carry;
@@ -290,7 +235,7 @@ __global__ void __launch_bounds__(1024) k_hf_tile_scan(uint32_t* __restrict__ ti
       bits += i < ntiles ? tile_bits[i] : 0u;
       sum += v[k];
     }
-    const uint32_t inc = wave_incl_scan(sum, lane);
+    const uint32_t inc = hfd::wave_incl_scan(sum);
     if (lane == 63) s_wave[wid] = inc;
     __syncthreads();
     uint32_t run = s_carry;
@@ -330,7 +275,7 @@ __global__ void __launch_bounds__(256) k_hf_gather(HfEncodeArgs a, int cellcap, 
   if (wid == 0) {
     const int c = c0 + lane;
     const uint32_t nc = c < a.pardeg ? (a.par_nbit[c] + 31) >> 5 : 0u;
-    const uint32_t inc = wave_incl_scan(nc, lane);
+    const uint32_t inc = hfd::wave_incl_scan(nc);
     const uint32_t off = tile_off[t] + inc - nc;
     s_ent[lane] = off, s_nc[lane] = nc;
     if (c < a.pardeg) a.par_entry[c] = off;
@@ -387,14 +332,6 @@ __device__ __forceinline__ uint32_t lut_pack(uint32_t nsym, uint32_t bits, uint3
   return (nsym << 30) | (bits << 25) | (l0 << 20) | (s1 << 10) | s0;
 }
 
-__device__ __forceinline__ int longest_code(const uint32_t* entry)
-{
-  int m = 1;  // last l with a code (entry[l+1] > entry[l])
-  for (int l = 1; l < 31; l++)
-    if (entry[l + 1] > entry[l]) m = l;
-  return m;
-}
-
 // One symbol from a left-justified window, reference rule (hf_kernels.cuhip.inl:351-365: the
 // first length l with prefix_l >= first[l]).  The thresholds first[l] * 2^(32-l) never increase
 // with l (canonical construction: first[l] >= (first[l+1] + count[l+1]) / 2), so the lengths
@@ -422,7 +359,7 @@ __global__ void __launch_bounds__(1024) k_hf_tables(const uint8_t* revbook, int 
   const uint16_t* keys = reinterpret_cast<const uint16_t*>(revbook + 256);
   for (int i = tid; i < bklen; i += blockDim.x) s_keys[i] = keys[i];
   __syncthreads();
-  const int maxl = longest_code(s_entry);
+  const int maxl = hfd::longest_code(s_entry);
   if (tid < 32) {
     tab[kTabFirst + tid] = (tid >= 1 && tid <= maxl) ? s_first[tid] : 0u;  // slow path
     s_base[tid] = s_entry[tid] - s_first[tid];
@@ -460,12 +397,6 @@ __global__ void __launch_bounds__(1024) k_hf_tables(const uint8_t* revbook, int 
     }
     tab[kTabL2 + q] = e;
   }
-}
-
-__device__ __forceinline__ void wave_sync()
-{
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
 }
 
 struct HfTables {
@@ -909,7 +840,7 @@ __global__ void __launch_bounds__(64 * kDecWaves) k_hf_decode(HfDecodeArgs a, in
     if (ncell + 2 <= (uint32_t)cellcap) {
       for (uint32_t i = lane; i < ncell; i += 64) cells[i] = src[i];
       if (lane < 2) cells[ncell + lane] = 0;
-      wave_sync();
+      hfd::wave_sync();
       pf.mark(0);
       decode_chunk<false>(cells, ncell, nbit, nsym, tb, outs, lane, pf);
     }
@@ -917,12 +848,12 @@ __global__ void __launch_bounds__(64 * kDecWaves) k_hf_decode(HfDecodeArgs a, in
       pf.mark(0);
       decode_chunk<true>(src, ncell, nbit, nsym, tb, outs, lane, pf);
     }
-    wave_sync();
+    hfd::wave_sync();
     uint16_t* dst = a.out + obase;
     const uint32_t n8 = (obase & 7) ? 0u : nsym >> 3;  // 16-B stores only when aligned
     for (uint32_t i = lane; i < n8; i += 64) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(outs)[i];
     for (uint32_t i = (n8 << 3) + lane; i < nsym; i += 64) dst[i] = outs[i];
-    wave_sync();
+    hfd::wave_sync();
     pf.mark(4);
   }
 #ifdef CUSZ_AMD_DEC_PROFILE

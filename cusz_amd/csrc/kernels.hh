@@ -202,7 +202,7 @@ template <typename T>
 int launch_spline3_x(SplineXArgs<T> a, const uint32_t* cells, size_t ncell, uint32_t* scratch, hipStream_t st);
 size_t spline_x_scratch_words(uint32_t ntiles, size_t ncell);
 
-// ---- fused brick pipeline (brick.hip) --------------------------------------------------------
+// ---- fused brick pipeline (brick_scan / brick_pack / brick_decode / brick_stream .hip) ----------
 // A wave owns a W x 8 x 8 brick (W = 64 V); the Huffman chunk length equals W so each brick row
 // is one chunk.  Eligible: 3-D with lx % W == 0, and 1-D (a brick = 64 consecutive chunks, 16
 // tiles of 1024; the last brick and chunk may be short).
@@ -234,7 +234,7 @@ int brick_configure(BrickLaunch& L, int elem_bytes, int device);
 // wave that completes the sample publishes it to the host (pub_dst, then *pub_flag = pub_epoch),
 // which builds the codebook while pass 1 goes on.  hist == nullptr: no sample, bricks in index order.
 // 3-D bricks count relaxed, and the completing wave accepts the sample once its bins sum to total
-// (brick.hip finish_unit); linear bricks count with an agent-scope acq_rel and do not use total.
+// (brick_scan.hip finish_unit); linear bricks count with an agent-scope acq_rel and do not use total.
 // the sample histogram's bins lie a 64-B line apart: the sample bricks finish together (first
 // round of pass 1) and their atomics would otherwise queue on the one or two memory channels of
 // a dense 4 KB array (measured: pass 1 +60 us)
@@ -267,7 +267,7 @@ int launch_brick_scan(const BrickLaunch& L, const T* in, double eb, int radius, 
                       const OutlierSink& ol,
                       uint32_t* hist, uint16_t* bhist, const BrickCodes& bc, int bklen, hipStream_t st,
                       const HostPub& pub = HostPub{});
-// archive plan (brick.hip k_brick_plan): region sizes, cell / outlier offsets, totals, headers
+// archive plan (brick_pack.hip k_brick_plan): region sizes, cell / outlier offsets, totals, headers
 struct BrickPlanArgs {
   const uint16_t* bhist;  // per-brick histograms, stride brick_hist_stride(bklen)
   int bklen, bhs;
@@ -323,7 +323,7 @@ struct BrickSingle {
   int rv_words;
   uint32_t* book_flag;         // device word (never reset)
 };
-// single-pass mode (brick.hip): the sample histogram into hist (u32[kMaxBklen * kSampleBinStride],
+// single-pass mode (brick_stream.hip): the sample histogram into hist (u32[kMaxBklen * kSampleBinStride],
 // zeroed; bins one line apart); its last workgroup (ticket: kPubTicketWords words, zeroed) copies
 // it to the host-mapped h_hist and sets *flag = epoch; the host builds the codebook.  Then the
 // streaming pass, which takes the host's book behind a device-polled gate (+ finish: outlier

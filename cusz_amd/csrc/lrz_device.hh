@@ -1,5 +1,5 @@
 // cusz_amd/csrc/lrz_device.hh -- Lorenzo device helpers shared by lorenzo.hip (brick-wise
-// kernels over a code buffer) and brick.hip (fused predict+encode / decode+reconstruct).
+// kernels over a code buffer) and brick_*.hip (fused predict+encode / decode+reconstruct).
 //
 // Semantics restate the reference GPU kernels: prequant/quantize lrz_c.cuhip.inl:50-89,
 // 216-260, 305-331; ZigZag composite.hh:61-84; reconstruct scans lrz_x.cuhip.inl +

@@ -110,7 +110,7 @@ struct Pipeline {
   int elem_bytes = 4;
 
   LorenzoGeom geom{};
-  BrickLaunch bl{};               // fused brick path (brick.hip); bl.g.ok when eligible
+  BrickLaunch bl{};               // fused brick path (brick_*.hip); bl.g.ok when eligible
   int layout = 0;                 // PSZ_AMD_LAYOUT_*: 0 brick layout when eligible, 1 reference layout
   bool layout_set = false;        // PSZ_AMD_LAYOUT_BRICK_FORCE: bricks also for small 2-D fields
   int codebook = PSZ_AMD_CODEBOOK_SAMPLED;  // PSZ_AMD_CODEBOOK_*: sampled device book (default),
@@ -191,7 +191,7 @@ struct Pipeline {
   uint32_t* hist_ticket() { return reinterpret_cast<uint32_t*>(d_small + 160); }
   uint32_t* summary_ticket() { return reinterpret_cast<uint32_t*>(d_small + 196); }
   uint32_t* plan_ticket() { return reinterpret_cast<uint32_t*>(d_small + 112); }
-  // the single-pass mode's codebook flag (brick.hip k_brick3_stream): never zeroed, epoch-compared
+  // the single-pass mode's codebook flag (brick_stream.hip k_brick3_stream): never zeroed, epoch-compared
   uint32_t* book_flag() { return reinterpret_cast<uint32_t*>(d_small + 240); }
   static constexpr uint32_t kStreamSlots = 8;  // outlier slots per brick in the single-pass mode (one per y-step)
   static constexpr size_t kSmallZeroBytes = 232;
@@ -225,7 +225,7 @@ struct Pipeline {
   }
 
   size_t rvbk_bytes(int bklen) const { return 4 * 64 + 2 * (size_t)bklen; }
-  // outlier slot per brick unit (brick.hip kUnitBricks bricks): 10 % of its elements + 16 at
+  // outlier slot per brick unit (brick_device.hh kUnitBricks bricks): 10 % of its elements + 16 at
   // first; a compress whose bricks spill grows it to the largest brick's count (grow_slots)
   uint32_t brick_slot_cap = 0;
   uint32_t brick_cap() const { return brick_slot_cap; }
@@ -565,11 +565,8 @@ struct Pipeline {
       return PSZ_SUCCESS;
     }
 
-    const size_t anchor_bytes = spl ? sizeof(T) * sgeom.anchor_len : 0;
     uint64_t* slots = spl ? d_spl_slots : d_slots;
     uint32_t* bcnt = spl ? d_spl_cnt : d_brick_cnt;
-    uint32_t* boff = spl ? d_spl_off : d_brick_off;
-    const uint32_t nbr = spl ? sgeom.ntiles : geom.nbricks;
     const uint32_t cap = spl ? spl_cap : cap_per_brick;
     OutlierSink ol{slots, bcnt, d_spill, spill_cnt(), cap, spill_cap, spl ? d_spl_sps : nullptr};
     if (spl) {
@@ -733,7 +730,7 @@ struct Pipeline {
     return finish_compress(h, out, outlen);
   }
 
-  // Fused brick compress (brick.hip): pass 1 (histograms + outliers) -> host codebook ->
+  // Fused brick compress (brick_scan.hip, brick_pack.hip): pass 1 (histograms + outliers) -> host codebook ->
   // region reservation -> pass 2 (predict + pack straight into the archive) -> finalize.
   BrickCodes brick_codes(bool zz, int radius) const
   {
@@ -1122,7 +1119,7 @@ struct Pipeline {
     return PSZ_SUCCESS;
   }
 
-  // fused decode + reconstruct (brick.hip): any archive whose chunk length is the brick width
+  // fused decode + reconstruct (brick_decode.hip): any archive whose chunk length is the brick width
   template <typename T>
   int decompress_brick(const psz_header* h, const uint8_t* in, T* out, bool zz, const BrickOutliers& bo)
   {
@@ -1145,7 +1142,7 @@ struct Pipeline {
   }
 
   // The box of e elements at o into `out` (cusz_amd.h psz_amd_decompress_region_*).  FUSED: only
-  // the covering bricks are decoded (brick.hip k_brick3_region), which needs the fused 3-D
+  // the covering bricks are decoded (brick_decode.hip k_brick3_region), which needs the fused 3-D
   // decoder's conditions and ranked outlier cells -- the bounds pass's verdict is the one word
   // read back here, before the decode is queued.  FALLBACK: the whole field into a scratch
   // field, then the box copied out.
