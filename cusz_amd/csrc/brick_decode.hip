@@ -1272,14 +1272,13 @@ int launch_brick_cell_bounds(const BrickLaunch& L, const uint32_t* cells, size_t
 }
 
 template <typename T>
-int launch_brick_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t bs_words, const uint8_t* revbook,
-                        int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, T* out, double eb, int radius,
-                        bool zz, const BrickOutliers& ol, hipStream_t st)
+int launch_brick_decode(const BrickLaunch& L, const PhfView& v, T* out, double eb, int radius, bool zz,
+                        const BrickOutliers& ol, hipStream_t st)
 {
   const T ebx2 = (T)(eb * 2);  // lrz_x.cuhip.inl:432
   const T r = (T)radius;
   const BrickGeom& g = L.g;
-  if (bs_words >= (1ull << 30)) return (int)hipErrorInvalidValue;
+  if (v.bs_words >= (1ull << 30)) return (int)hipErrorInvalidValue;
   if (g.ndim == 1) {
     const uint32_t ntiles = (uint32_t)((g.n + 1023) / 1024), nunits = (ntiles + 63) / 64;
     // waves per CU: the static unit assignment ends when the busiest wave's units are done, and
@@ -1293,17 +1292,17 @@ int launch_brick_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t 
     const uint32_t grid = (uint32_t)std::max<size_t>(1, std::min<size_t>(L.ncu, (nunits + wpb - 1) / wpb));
     const size_t lds1 = (size_t)wpb * kD1WaveBytes;
     if (zz)
-      k_brick1_decode<T, true><<<grid, 64 * wpb, lds1, st>>>(bitstream, (uint32_t)bs_words, revbook, bklen, par_nbit,
-                                                             par_entry, out, g.n, ebx2, r, g.nchunks, nunits, ol);
+      k_brick1_decode<T, true><<<grid, 64 * wpb, lds1, st>>>(v.bitstream, (uint32_t)v.bs_words, v.revbook, v.bklen, v.par_nbit,
+                                                             v.par_entry, out, g.n, ebx2, r, g.nchunks, nunits, ol);
     else
-      k_brick1_decode<T, false><<<grid, 64 * wpb, lds1, st>>>(bitstream, (uint32_t)bs_words, revbook, bklen, par_nbit,
-                                                              par_entry, out, g.n, ebx2, r, g.nchunks, nunits, ol);
+      k_brick1_decode<T, false><<<grid, 64 * wpb, lds1, st>>>(v.bitstream, (uint32_t)v.bs_words, v.revbook, v.bklen, v.par_nbit,
+                                                              v.par_entry, out, g.n, ebx2, r, g.nchunks, nunits, ol);
     return (int)hipGetLastError();
   }
   // buffer stores address a brick block with 32-bit offsets from its first element
   const size_t plane = (size_t)L.lx * L.ly;
   const bool buf = (7 * plane + 7 * (size_t)L.lx + (size_t)kBlk) * sizeof(T) < (1ull << 31);
-  const uint32_t bw = (uint32_t)bs_words;
+  const uint32_t bw = (uint32_t)v.bs_words;
   // 32-column blocks pay once the bricks fill the 12-wave slots (a 512^3 field); a small slab,
   // one brick per wave, is bound by one brick's latency, which the 64-column blocks keep shorter
   // (512 x 512 x 64: 88 against 94 us)
@@ -1312,8 +1311,8 @@ int launch_brick_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t 
     constexpr int B3 = decltype(blk)::value;
     const size_t lds = (size_t)Dec3Cfg<B3>::kWaves * Dec3Cfg<B3>::kWaveBytes;  // dynamic part
 #define DEC_LAUNCH(ZZ, BUF)                                                                                     \
-    k_brick3_decode<T, ZZ, BUF, B3><<<L.ncu, 64 * Dec3Cfg<B3>::kWaves, lds, st>>>(bitstream, bw, revbook, bklen, par_nbit, \
-                                                                              par_entry, out, L.lx, L.ly, L.lz, ebx2, r, \
+    k_brick3_decode<T, ZZ, BUF, B3><<<L.ncu, 64 * Dec3Cfg<B3>::kWaves, lds, st>>>(v.bitstream, bw, v.revbook, v.bklen, v.par_nbit, \
+                                                                              v.par_entry, out, L.lx, L.ly, L.lz, ebx2, r, \
                                                                               g.nbx, g.nby, g.nbricks, ol)
     if (zz) {
       if (buf) DEC_LAUNCH(true, true); else DEC_LAUNCH(true, false);
@@ -1342,14 +1341,12 @@ RegionBox region_box(uint32_t ox, uint32_t oy, uint32_t oz, uint32_t ex, uint32_
 }
 
 template <typename T>
-int launch_brick_region(const BrickLaunch& L, const uint32_t* bitstream, size_t bs_words, const uint8_t* revbook,
-                        int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, T* out_box, double eb,
-                        int radius, const BrickOutliers& ol, const uint32_t (&o)[3], const uint32_t (&e)[3],
-                        hipStream_t st)
+int launch_brick_region(const BrickLaunch& L, const PhfView& v, T* out_box, double eb, int radius,
+                        const BrickOutliers& ol, const uint32_t (&o)[3], const uint32_t (&e)[3], hipStream_t st)
 {
   const BrickGeom& g = L.g;
   // the box lies inside the field, so its covering bricks lie inside the brick grid
-  if (!g.ok || g.ndim != 3 || g.W != 256 || bs_words >= (1ull << 30) || bklen < 1 || bklen > kMaxBklen || !e[0] ||
+  if (!g.ok || g.ndim != 3 || g.W != 256 || v.bs_words >= (1ull << 30) || v.bklen < 1 || v.bklen > kMaxBklen || !e[0] ||
       !e[1] || !e[2] || o[0] >= L.lx || e[0] > L.lx - o[0] || o[1] >= L.ly || e[1] > L.ly - o[1] || o[2] >= L.lz ||
       e[2] > L.lz - o[2])
     return (int)hipErrorInvalidValue;
@@ -1362,17 +1359,16 @@ int launch_brick_region(const BrickLaunch& L, const uint32_t* bitstream, size_t 
   // region is bound by one brick's serial walk, not by throughput
   const uint32_t grid = std::max(1u, std::min((uint32_t)L.ncu, items));
   const size_t lds = (size_t)C::kWaves * C::kWaveBytes;  // dynamic part
-  k_brick3_region<T><<<grid, 64 * C::kWaves, lds, st>>>(bitstream, (uint32_t)bs_words, revbook, bklen, par_nbit,
-                                                        par_entry, out_box, L.lx, L.ly, L.lz, ebx2, r, g.nbx, g.nby,
+  k_brick3_region<T><<<grid, 64 * C::kWaves, lds, st>>>(v.bitstream, (uint32_t)v.bs_words, v.revbook, v.bklen, v.par_nbit,
+                                                        v.par_entry, out_box, L.lx, L.ly, L.lz, ebx2, r, g.nbx, g.nby,
                                                         ol, box);
   return (int)hipGetLastError();
 }
 
-int launch_chunk_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t bs_words, const uint8_t* revbook,
-                        int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, uint16_t* codes, size_t n,
-                        uint32_t nchunks, uint32_t sublen, hipStream_t st)
+int launch_chunk_decode(const BrickLaunch& L, const PhfView& v, uint16_t* codes, size_t n, hipStream_t st)
 {
-  if (bs_words >= (1ull << 30) || bklen < 1 || bklen > kMaxBklen || sublen % kBlk != 0 || sublen == 0)
+  const uint32_t nchunks = (uint32_t)v.pardeg, sublen = (uint32_t)v.sublen;
+  if (v.bs_words >= (1ull << 30) || v.bklen < 1 || v.bklen > kMaxBklen || sublen % kBlk != 0 || sublen == 0)
     return (int)hipErrorInvalidValue;
   if (!nchunks) return (int)hipSuccess;
   // Fewer units than 8 per CU (a 2-D field of a few million values): spread them over every CU,
@@ -1383,8 +1379,8 @@ int launch_chunk_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t 
   const uint32_t wpb = std::min<uint32_t>(kDecWaves, (units + ncu - 1) / ncu);
   const size_t lds = (size_t)wpb * kD4Cells;
   const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(ncu, (units + wpb - 1) / wpb));
-  k_chunk_decode<0><<<grid, 64 * kDecWaves, lds, st>>>(bitstream, (uint32_t)bs_words, revbook, bklen, par_nbit,
-                                                       par_entry, codes, n, nchunks, sublen, wpb);
+  k_chunk_decode<0><<<grid, 64 * kDecWaves, lds, st>>>(v.bitstream, (uint32_t)v.bs_words, v.revbook, v.bklen, v.par_nbit,
+                                                       v.par_entry, codes, n, nchunks, sublen, wpb);
   return (int)hipGetLastError();
 }
 
@@ -1402,11 +1398,9 @@ extern "C" int psz_amd_debug_brick_profile(unsigned long long* host, int reset)
 #endif
 
 #define INST(T)                                                                                                   \
-  template int launch_brick_decode<T>(const BrickLaunch&, const uint32_t*, size_t, const uint8_t*, int,            \
-                                      const uint32_t*, const uint32_t*, T*, double, int, bool, const BrickOutliers&, \
+  template int launch_brick_decode<T>(const BrickLaunch&, const PhfView&, T*, double, int, bool, const BrickOutliers&, \
                                       hipStream_t);                                                                \
-  template int launch_brick_region<T>(const BrickLaunch&, const uint32_t*, size_t, const uint8_t*, int,            \
-                                      const uint32_t*, const uint32_t*, T*, double, int, const BrickOutliers&,     \
+  template int launch_brick_region<T>(const BrickLaunch&, const PhfView&, T*, double, int, const BrickOutliers&,   \
                                       const uint32_t(&)[3], const uint32_t(&)[3], hipStream_t);
 INST(float)
 INST(double)

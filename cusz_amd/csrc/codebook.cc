@@ -18,6 +18,8 @@
 #include <cstring>
 #include <vector>
 
+#include "archive_layout.hh"
+
 namespace cusz_amd {
 
 namespace {
@@ -171,7 +173,7 @@ int canonize(const uint8_t* len, int max_l, int bklen, uint32_t* book, uint8_t* 
     keys[slot] = (uint16_t)s;
     book[s] = ((uint32_t)(first[l] + slot - entry[l]) & 0x07FFFFFFu) | ((uint32_t)l << 27);
   }
-  const int bytes = 4 * 64 + 2 * bklen;
+  const int bytes = (int)rvbk_bytes(bklen);
   std::memset(revbook, 0, bytes);
   std::memcpy(revbook, first, 128);
   std::memcpy(revbook + 128, entry, 128);

@@ -1,6 +1,7 @@
 // cusz_amd/csrc/kernels.hh -- launchers of the hand-written gfx950 kernels.
 #pragma once
 
+#include "archive_layout.hh"
 #include "common.hh"
 
 namespace cusz_amd {
@@ -87,7 +88,7 @@ size_t hf_encode_temp_words(int sublen, int pardeg);
 constexpr int kHfDecTableWords = 4096 + 128 + 2048;
 constexpr int kHfDecScratchWords = kHfDecTableWords + 16;
 
-struct HfDecodeArgs {
+struct HfDecodeArgs {  // its first five fields: a PhfView's (archive_layout.hh)
   const uint32_t* bitstream;
   const uint8_t* revbook;  // first i32[32] | entry i32[32] | keys u16[bklen]
   int bklen;
@@ -349,13 +350,10 @@ int launch_brick_cell_bounds(const BrickLaunch& L, const uint32_t* cells, size_t
                              uint32_t* unsorted, uint32_t epoch, hipStream_t st);
 // decode only, any archive whose chunk length is a multiple of 64: chunk c's codes to
 // codes[sublen c ...] (index order)
-int launch_chunk_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t bs_words, const uint8_t* revbook,
-                        int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, uint16_t* codes, size_t n,
-                        uint32_t nchunks, uint32_t sublen, hipStream_t st);
+int launch_chunk_decode(const BrickLaunch& L, const PhfView& v, uint16_t* codes, size_t n, hipStream_t st);
 template <typename T>
-int launch_brick_decode(const BrickLaunch& L, const uint32_t* bitstream, size_t bs_words, const uint8_t* revbook,
-                        int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, T* out, double eb, int radius,
-                        bool zz, const BrickOutliers& ol, hipStream_t st);
+int launch_brick_decode(const BrickLaunch& L, const PhfView& v, T* out, double eb, int radius, bool zz,
+                        const BrickOutliers& ol, hipStream_t st);
 
 // Region decode (3-D brick fields, Lorenzo, ranked cells -- the caller has read the bounds pass's
 // verdict): the box of e elements at o, decoded from its covering bricks only into out_box, a
@@ -366,10 +364,8 @@ struct RegionBox {
 };
 RegionBox region_box(uint32_t ox, uint32_t oy, uint32_t oz, uint32_t ex, uint32_t ey, uint32_t ez, uint32_t W);
 template <typename T>
-int launch_brick_region(const BrickLaunch& L, const uint32_t* bitstream, size_t bs_words, const uint8_t* revbook,
-                        int bklen, const uint32_t* par_nbit, const uint32_t* par_entry, T* out_box, double eb,
-                        int radius, const BrickOutliers& ol, const uint32_t (&o)[3], const uint32_t (&e)[3],
-                        hipStream_t st);
+int launch_brick_region(const BrickLaunch& L, const PhfView& v, T* out_box, double eb, int radius,
+                        const BrickOutliers& ol, const uint32_t (&o)[3], const uint32_t (&e)[3], hipStream_t st);
 // out_box[(z ey + y) ex + x] = field[((oz + z) ly + oy + y) lx + ox + x] (the region fallback)
 template <typename T>
 int launch_crop_box(const T* field, size_t lx, size_t ly, const size_t (&o)[3], const size_t (&e)[3], T* out_box,

@@ -20,11 +20,12 @@
 #include <cstring>
 #include <vector>
 
-#include "cusz/header.h"
+#include "archive_layout.hh"
 #include "cusz_amd.h"
-#include "hf.h"
 
 namespace {
+
+using cusz_amd::rvbk_bytes;
 
 struct Part {
   psz_header h;
@@ -33,8 +34,6 @@ struct Part {
   const uint8_t* phf;
   size_t n;
 };
-
-size_t rvbk_bytes(int bklen) { return 4 * 64 + 2 * (size_t)bklen; }
 
 int ndim_of(psz_len l) { return l.z > 1 ? 3 : (l.y > 1 ? 2 : 1); }
 
@@ -130,25 +129,13 @@ extern "C" int psz_amd_merge_archives(const uint8_t* const* parts, const size_t*
     return PSZ_ABORT_UNSUPPORTED_DIMENSION;
 
   const int bklen = P[0].ph.bklen;
-  const size_t rv = rvbk_bytes(bklen);
-  phf_header ph;
-  std::memset(&ph, 0, sizeof(ph));
-  ph.bklen = bklen, ph.sublen = P[0].ph.sublen, ph.pardeg = (int)pardeg, ph.original_len = n_total;
-  ph.total_nbit = nbit, ph.total_ncell = ncell;
-  ph.entry[PHFHEADER_HEADER] = 0;
-  ph.entry[PHFHEADER_RVBK] = PHFHEADER_FORCED_ALIGN;
-  ph.entry[PHFHEADER_PAR_NBIT] = (uint32_t)(PHFHEADER_FORCED_ALIGN + rv);
-  ph.entry[PHFHEADER_PAR_ENTRY] = (uint32_t)(ph.entry[PHFHEADER_PAR_NBIT] + 4 * pardeg);
-  ph.entry[PHFHEADER_BITSTREAM] = (uint32_t)(ph.entry[PHFHEADER_PAR_ENTRY] + 4 * pardeg);
-  ph.entry[PHFHEADER_END] = (uint32_t)(ph.entry[PHFHEADER_BITSTREAM] + 4 * ncell);
-
+  const cusz_amd::PhfLayout lay(0, bklen, pardeg);  // no anchors: checked per part above
   psz_header h = P[0].h;
-  h.len = full_len;
+  phf_header ph;
+  cusz_amd::fill_header_templates(lay, bklen, P[0].ph.sublen, (int)pardeg, n_total, full_len, &h, &ph);
+  ph.total_nbit = nbit, ph.total_ncell = ncell;
+  ph.entry[PHFHEADER_END] = (uint32_t)(lay.bits_rel + 4 * ncell);
   h.splen = splen;
-  h.vle_sublen = ph.sublen, h.vle_pardeg = (int)pardeg;
-  h.entry[PSZHEADER_HEADER] = 0;
-  h.entry[PSZHEADER_ANCHOR] = sizeof(psz_header);
-  h.entry[PSZHEADER_ENCODED] = sizeof(psz_header);
   h.entry[PSZHEADER_SPFMT] = h.entry[PSZHEADER_ENCODED] + ph.entry[PHFHEADER_END];
   h.entry[PSZHEADER_ENC_PASS1_END] = (uint32_t)(h.entry[PSZHEADER_SPFMT] + 8 * splen);
   h.entry[PSZHEADER_ENC_PASS2_END] = h.entry[PSZHEADER_ENC_PASS1_END];
@@ -166,7 +153,7 @@ extern "C" int psz_amd_merge_archives(const uint8_t* const* parts, const size_t*
   std::memcpy(out, &h, sizeof(h));
   std::memset(phf, 0, PHFHEADER_FORCED_ALIGN);
   std::memcpy(phf, &ph, sizeof(ph));
-  std::memcpy(phf + PHFHEADER_FORCED_ALIGN, P[0].phf + PHFHEADER_FORCED_ALIGN, rv);
+  std::memcpy(phf + PHFHEADER_FORCED_ALIGN, P[0].phf + PHFHEADER_FORCED_ALIGN, lay.rvbk);
   uint32_t* nbit_out = reinterpret_cast<uint32_t*>(phf + ph.entry[PHFHEADER_PAR_NBIT]);
   uint32_t* entry_out = reinterpret_cast<uint32_t*>(phf + ph.entry[PHFHEADER_PAR_ENTRY]);
   uint8_t* bits_out = phf + ph.entry[PHFHEADER_BITSTREAM];

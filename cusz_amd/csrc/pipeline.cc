@@ -13,15 +13,23 @@
 //
 // The reference does 5+ host round trips per compress and copies a 2N-byte buffer
 // (SURVEY.md §3.1); here the archive is assembled in place.
+//
+// What the compress and decode paths share is defined once: the phf segment's offsets and the
+// header templates in archive_layout.hh (PhfLayout to write, PhfView to read), the codebook's
+// trip through the host and its stream gate in Pipeline::BookGate / book_stage, the small device
+// buffer and the host read-back area as the structs SmallBuf / Readback, and every device
+// allocation in a DevBuf that frees itself.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <tuple>
 
+#include "archive_layout.hh"
 #include "common.hh"
 #include "cusz.h"
 #include "cusz_amd.h"
@@ -100,6 +108,69 @@ static void tune_chunking(size_t n, int device, int* sublen, int* pardeg)
   *pardeg = (int)((std::max<size_t>(n, 1) - 1) / s + 1);
 }
 
+// An allocation that frees itself (device memory; Free = hipHostFree: pinned host memory).
+template <typename T, hipError_t (*Free)(void*) = hipFree>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { free(); }
+  hipError_t alloc(size_t count) { return free(), hipMalloc(&p, count * sizeof(T)); }  // frees what it holds first
+  void free() { if (p) (void)Free(p), p = nullptr; }
+  operator T*() const { return p; }
+};
+
+struct Event {  // likewise
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  operator hipEvent_t() const { return e; }
+};
+
+// The small device buffer (Pipeline::d_small).  Bytes [0, kSmallZeroBytes) are zeroed at the start
+// of every compress; the tickets are the 9-word publish tickets of pub_device.hh.
+struct SmallBuf {
+  uint32_t spill_cnt, pad0[3];
+  unsigned int timeout, pad1[11];
+  CompressInfo info;
+  uint32_t plan_ticket[9], pad2[3];
+  uint32_t hist_ticket[9];
+  uint32_t summary_ticket[9];
+  uint32_t pad3[2];
+  uint32_t book_flag, pad4[3];  // the single-pass mode's codebook flag (brick_stream.hip k_brick3_stream):
+                                // never zeroed, epoch-compared
+  double minmax[2];
+  uint8_t pad5[240];
+  unsigned int ext_scratch[2 * 1024 * 2];  // extrema scratch
+  uint32_t dec_lut[kHfDecScratchWords];
+};
+constexpr size_t kSmallBytes = sizeof(SmallBuf);
+constexpr size_t kSmallZeroBytes = offsetof(SmallBuf, summary_ticket) + sizeof(SmallBuf::summary_ticket);
+static_assert(offsetof(SmallBuf, spill_cnt) == 0 && offsetof(SmallBuf, timeout) == 16 && offsetof(SmallBuf, info) == 64 &&
+                  offsetof(SmallBuf, plan_ticket) == 112 && offsetof(SmallBuf, hist_ticket) == 160 &&
+                  offsetof(SmallBuf, summary_ticket) == 196 && offsetof(SmallBuf, book_flag) == 240 &&
+                  offsetof(SmallBuf, minmax) == 256 && offsetof(SmallBuf, ext_scratch) == 512 &&
+                  offsetof(SmallBuf, dec_lut) == 512 + 2 * 1024 * 8 && kSmallZeroBytes == 232 &&
+                  kSmallBytes == 512 + 2 * 1024 * 8 + kHfDecScratchWords * 4,
+              "small-buffer layout");
+
+// The 1 KB read-back area of the host-mapped transfer buffer (Pipeline::h_readback): what the
+// publish kernels copy to the host.
+struct Readback {
+  uint8_t header[sizeof(psz_header)], pad0[80];  // the archive's psz header
+  CompressInfo info;
+  uint8_t pad1[80];
+  unsigned int timeout, pad2[15];
+  uint32_t excess, pad3[15];  // a sharded finish's summed overflow word
+  double minmax[2];           // Rel mode's extrema
+};
+static_assert(offsetof(Readback, header) == 0 && offsetof(Readback, info) == 256 && offsetof(Readback, timeout) == 384 &&
+                  offsetof(Readback, excess) == 448 && offsetof(Readback, minmax) == 512 && sizeof(Readback) <= 1024,
+              "read-back layout");
+
 struct Pipeline {
   psz_dtype dtype;
   psz_len len;
@@ -115,23 +186,23 @@ struct Pipeline {
   bool layout_set = false;        // PSZ_AMD_LAYOUT_BRICK_FORCE: bricks also for small 2-D fields
   int codebook = PSZ_AMD_CODEBOOK_SAMPLED;  // PSZ_AMD_CODEBOOK_*: sampled device book (default),
                                             // reference book (exact), streaming single pass
-  uint32_t* d_shist = nullptr;    // pass 1's codebook sample: strided histogram + counter
-  uint16_t* d_bhist = nullptr;    // per-brick u16 histograms (pass 1 -> reservation)
-  uint32_t* d_ub = nullptr;       // per-brick region upper bounds (cells)
-  uint32_t* d_bbase = nullptr;    // per-brick cell offsets inside their plan block
-  uint32_t* d_plan = nullptr;     // plan block prefixes: cells | outliers (nblk + 1 each)
+  DevBuf<uint32_t> d_shist;       // pass 1's codebook sample: strided histogram + counter
+  DevBuf<uint16_t> d_bhist;       // per-brick u16 histograms (pass 1 -> reservation)
+  DevBuf<uint32_t> d_ub;          // per-brick region upper bounds (cells)
+  DevBuf<uint32_t> d_bbase;       // per-brick cell offsets inside their plan block
+  DevBuf<uint32_t> d_plan;        // plan block prefixes: cells | outliers (nblk + 1 each)
   SplineGeom sgeom{};
   uint32_t spl_cap = 0;           // outlier slots per spline tile
   size_t spl_slot_cells = 0;      // capacity of the spline slot area (allocated on first use)
-  uint64_t* d_spl_slots = nullptr;
-  uint32_t* d_spl_cnt = nullptr;  // per-tile outlier counts | offsets
-  uint32_t* d_spl_off = nullptr;
-  uint32_t* d_spl_sps = nullptr;  // per-tile spill range starts
-  uint32_t* d_spl_x = nullptr;    // decompression buckets
-  uint32_t* d_x1d = nullptr;      // 1-D decompression: per-brick first outlier cell + unsorted flag
+  DevBuf<uint64_t> d_spl_slots;
+  DevBuf<uint32_t> d_spl_cnt;     // per-tile outlier counts | offsets
+  DevBuf<uint32_t> d_spl_off;
+  DevBuf<uint32_t> d_spl_sps;     // per-tile spill range starts
+  DevBuf<uint32_t> d_spl_x;       // decompression buckets
+  DevBuf<uint32_t> d_x1d;         // 1-D decompression: per-brick first outlier cell + unsorted flag
   uint32_t cell_epoch = 0;        // tags the unsorted flag of the current decompress (never 0)
   uint32_t next_cell_epoch() { return cell_epoch = cell_epoch + 1 ? cell_epoch + 1 : 1; }
-  void* d_region_field = nullptr;  // region fallback: the whole field (allocated on first use)
+  DevBuf<uint8_t> d_region_field;  // region fallback: the whole field (allocated on first use)
   psz_amd_region_info last_region{};
   bool has_last_region = false;
   size_t spl_x_words = 0;
@@ -145,86 +216,52 @@ struct Pipeline {
   size_t splen = 0;
 
   // device
-  uint16_t* d_codes = nullptr;
-  uint8_t* d_codes8 = nullptr;     // brick layout: byte rows between the encode passes
-  uint64_t* d_rowmask = nullptr;   // brick layout: u16 rows per brick
-  uint32_t* d_hist = nullptr;
-  uint32_t* d_book = nullptr;
-  uint64_t* d_slots = nullptr;
-  uint32_t* d_brick_cnt = nullptr;
-  uint32_t* d_brick_off = nullptr;
-  uint64_t* d_spill = nullptr;
-  uint8_t* d_small = nullptr;  // spill_cnt | timeout | info | minmax | extrema scratch
-  unsigned long long* d_status = nullptr;
-  uint32_t* d_enc_temp = nullptr;  // encoder scratch (chunk cells at a worst-case stride)
+  DevBuf<uint16_t> d_codes;
+  DevBuf<uint8_t> d_codes8;        // brick layout: byte rows between the encode passes
+  DevBuf<uint64_t> d_rowmask;      // brick layout: u16 rows per brick
+  DevBuf<uint32_t> d_hist;
+  DevBuf<uint32_t> d_book;
+  DevBuf<uint64_t> d_slots;
+  DevBuf<uint32_t> d_brick_cnt;
+  DevBuf<uint32_t> d_brick_off;
+  DevBuf<uint64_t> d_spill;
+  DevBuf<SmallBuf> d_small;  // one SmallBuf
+  DevBuf<unsigned long long> d_status;
+  DevBuf<uint32_t> d_enc_temp;     // encoder scratch (chunk cells at a worst-case stride)
   size_t status_words = 0;
-  uint8_t* d_archive = nullptr;
+  DevBuf<uint8_t> d_archive;
   size_t archive_cap = 0;
 
   // pinned, host-mapped, coherent transfer area (kernels write it, the host polls flags)
-  uint8_t* h_xfer = nullptr;
+  DevBuf<uint8_t, hipHostFree> h_xfer;
   uint32_t epoch = 0;
   uint32_t gate_epoch = 0;       // host -> stream gate (flag 5): the upload kernel polls it
   uint32_t summary_epoch = 0;    // != 0: the compress summary is published by the pack kernel
   bool gate = true;              // brick encode queued behind a device-polled host gate (flag 5)
   static constexpr size_t kXferBytes = 16384;
-  volatile uint32_t* flag(int i) { return reinterpret_cast<volatile uint32_t*>(h_xfer) + i; }  // 0..15
-  uint32_t* h_hist() { return reinterpret_cast<uint32_t*>(h_xfer + 64); }               // 4 KB
-  uint32_t* h_book() { return reinterpret_cast<uint32_t*>(h_xfer + 64 + 4096); }        // 4 KB
-  uint8_t* h_revbook() { return h_xfer + 64 + 8192; }                                    // 2304 B
-  uint8_t* h_readback() const { return h_xfer + 64 + 8192 + 2560; }                            // 1 KB
+  volatile uint32_t* flag(int i) { return reinterpret_cast<volatile uint32_t*>(h_xfer.p) + i; }  // 0..15
+  uint32_t* h_hist() { return reinterpret_cast<uint32_t*>(h_xfer.p + 64); }               // 4 KB
+  uint32_t* h_book() { return reinterpret_cast<uint32_t*>(h_xfer.p + 64 + 4096); }        // 4 KB
+  uint8_t* h_revbook() { return h_xfer.p + 64 + 8192; }                                    // 2304 B
+  Readback* h_readback() const { return reinterpret_cast<Readback*>(h_xfer.p + 64 + 8192 + 2560); }  // 1 KB
 
   bool timing = false;
   bool broken = false;  // an allocation failed mid-call (grow_spill): every later compress fails
-  hipEvent_t ev[12] = {};
+  Event ev[12];
   float stage_ms[PSZ_AMD_T_COUNT] = {0};
 
-  uint32_t* spill_cnt() { return reinterpret_cast<uint32_t*>(d_small); }
-  unsigned int* timeout() { return reinterpret_cast<unsigned int*>(d_small + 16); }
-  CompressInfo* info() { return reinterpret_cast<CompressInfo*>(d_small + 64); }
-  double* minmax() { return reinterpret_cast<double*>(d_small + 256); }
-  unsigned int* ext_scratch() { return reinterpret_cast<unsigned int*>(d_small + 512); }
-  uint32_t* dec_lut() { return reinterpret_cast<uint32_t*>(d_small + 512 + 2 * 1024 * 8); }
-  static constexpr size_t kSmallBytes = 512 + 2 * 1024 * 8 + kHfDecScratchWords * 4;
-  // the publish tickets (9 words each, pub_device.hh); bytes [0, kSmallZeroBytes) are zeroed
-  // at the start of every compress
-  uint32_t* hist_ticket() { return reinterpret_cast<uint32_t*>(d_small + 160); }
-  uint32_t* summary_ticket() { return reinterpret_cast<uint32_t*>(d_small + 196); }
-  uint32_t* plan_ticket() { return reinterpret_cast<uint32_t*>(d_small + 112); }
-  // the single-pass mode's codebook flag (brick_stream.hip k_brick3_stream): never zeroed, epoch-compared
-  uint32_t* book_flag() { return reinterpret_cast<uint32_t*>(d_small + 240); }
+  uint32_t* spill_cnt() { return &d_small.p->spill_cnt; }
+  unsigned int* timeout() { return &d_small.p->timeout; }
+  CompressInfo* info() { return &d_small.p->info; }
+  double* minmax() { return d_small.p->minmax; }
+  unsigned int* ext_scratch() { return d_small.p->ext_scratch; }
+  uint32_t* dec_lut() { return d_small.p->dec_lut; }
+  uint32_t* hist_ticket() { return d_small.p->hist_ticket; }
+  uint32_t* summary_ticket() { return d_small.p->summary_ticket; }
+  uint32_t* plan_ticket() { return d_small.p->plan_ticket; }
+  uint32_t* book_flag() { return &d_small.p->book_flag; }
   static constexpr uint32_t kStreamSlots = 8;  // outlier slots per brick in the single-pass mode (one per y-step)
-  static constexpr size_t kSmallZeroBytes = 232;
-  static_assert(64 + sizeof(CompressInfo) <= 112 && 112 + 36 <= 160 && 196 + 36 <= kSmallZeroBytes &&
-                    kSmallZeroBytes <= 256,
-                "small-buffer layout");
 
-  ~Pipeline() { release(); }
-
-  void release()
-  {
-    if (d_shist) (void)hipFree(d_shist), d_shist = nullptr;
-    if (d_region_field) (void)hipFree(d_region_field), d_region_field = nullptr;
-    for (void* p : {(void*)d_codes, (void*)d_hist, (void*)d_book, (void*)d_slots, (void*)d_brick_cnt,
-                    (void*)d_brick_off, (void*)d_spill, (void*)d_small, (void*)d_status, (void*)d_archive,
-                    (void*)d_enc_temp, (void*)d_spl_slots, (void*)d_spl_cnt, (void*)d_spl_off, (void*)d_spl_x, (void*)d_spl_sps,
-                    (void*)d_bhist, (void*)d_ub, (void*)d_bbase, (void*)d_plan, (void*)d_x1d, (void*)d_codes8,
-                    (void*)d_rowmask})
-      if (p) (void)hipFree(p);
-    if (h_xfer) (void)hipHostFree(h_xfer);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e), e = nullptr;
-    d_codes = nullptr, d_hist = nullptr, d_book = nullptr, d_slots = nullptr, d_brick_cnt = nullptr;
-    d_brick_off = nullptr, d_spill = nullptr, d_small = nullptr, d_status = nullptr, d_archive = nullptr;
-    d_enc_temp = nullptr;
-    d_bhist = nullptr, d_ub = nullptr, d_bbase = nullptr, d_plan = nullptr, d_x1d = nullptr;
-    d_codes8 = nullptr, d_rowmask = nullptr;
-    d_spl_slots = nullptr, d_spl_cnt = nullptr, d_spl_off = nullptr, d_spl_x = nullptr, d_spl_sps = nullptr;
-    spl_slot_cells = 0, spl_x_words = 0;
-    h_xfer = nullptr;
-  }
-
-  size_t rvbk_bytes(int bklen) const { return 4 * 64 + 2 * (size_t)bklen; }
   // outlier slot per brick unit (brick_device.hh kUnitBricks bricks): 10 % of its elements + 16 at
   // first; a compress whose bricks spill grows it to the largest brick's count (grow_slots)
   uint32_t brick_slot_cap = 0;
@@ -276,7 +313,7 @@ struct Pipeline {
     if (ndim == 1) {
       // per-unit first cell + unsorted word: units of 16384 (reconstruction) or 256 (brick chunks)
       const size_t units = std::max<size_t>(geom.nbricks, (n + 255) / 256);
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_x1d, (units + 2) * 4));
+      CUSZ_AMD_HIP_CHECK(d_x1d.alloc(units + 2));
       CUSZ_AMD_HIP_CHECK(hipMemset(d_x1d, 0, (units + 2) * 4));  // unsorted word: no epoch yet
     }
     sgeom = spline_geom(l.x, l.y, l.z);
@@ -292,36 +329,36 @@ struct Pipeline {
       CUSZ_AMD_HIP_CHECK((hipError_t)brick_configure(bl, elem_bytes, device));
       brick_slot_cap = brick_unit_elems() / 10 + 16;
       max_bricks = std::max(max_bricks, bl.g.nbricks);
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_bhist, (size_t)bl.g.nbricks * kMaxBklen * sizeof(uint16_t)));
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_ub, (size_t)bl.g.nbricks * 4));
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_bbase, ((size_t)bl.g.nbricks + 1) * 4));
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_plan, 2 * ((size_t)brick_plan_blocks(bl.g.nbricks) + 1) * 4));
+      CUSZ_AMD_HIP_CHECK(d_bhist.alloc((size_t)bl.g.nbricks * kMaxBklen));
+      CUSZ_AMD_HIP_CHECK(d_ub.alloc(bl.g.nbricks));
+      CUSZ_AMD_HIP_CHECK(d_bbase.alloc((size_t)bl.g.nbricks + 1));
+      CUSZ_AMD_HIP_CHECK(d_plan.alloc(2 * ((size_t)brick_plan_blocks(bl.g.nbricks) + 1)));
       // fused decompression: per-brick first outlier cell + unsorted flag (d_x1d's role in 1-D)
       if (!d_x1d) {
-        CUSZ_AMD_HIP_CHECK(hipMalloc(&d_x1d, ((size_t)bl.g.nbricks + 2) * 4));
+        CUSZ_AMD_HIP_CHECK(d_x1d.alloc((size_t)bl.g.nbricks + 2));
         CUSZ_AMD_HIP_CHECK(hipMemset(d_x1d, 0, ((size_t)bl.g.nbricks + 2) * 4));
       }
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_codes8, (size_t)bl.g.nbricks * bl.g.brick_elems + 64));  // + 8-B load slack
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_rowmask, (size_t)bl.g.nbricks * 8));
+      CUSZ_AMD_HIP_CHECK(d_codes8.alloc((size_t)bl.g.nbricks * bl.g.brick_elems + 64));  // + 8-B load slack
+      CUSZ_AMD_HIP_CHECK(d_rowmask.alloc(bl.g.nbricks));
     }
 
     // codes: index order (reference layout) or brick order (brick layout: whole bricks)
     const size_t code_len = std::max(n + 64, bl.g.ok ? (size_t)bl.g.nbricks * bl.g.brick_elems : 0);
-    CUSZ_AMD_HIP_CHECK(hipMalloc(&d_codes, code_len * sizeof(uint16_t)));
-    CUSZ_AMD_HIP_CHECK(hipMalloc(&d_hist, (kMaxBklen + 4) * sizeof(uint32_t)));  // + the sharded overflow word
-    CUSZ_AMD_HIP_CHECK(hipMalloc(&d_book, kMaxBklen * sizeof(uint32_t)));
-    CUSZ_AMD_HIP_CHECK(hipMalloc(&d_slots, slot_cells_total() * 8));
-    CUSZ_AMD_HIP_CHECK(hipMalloc(&d_brick_cnt, (size_t)max_bricks * 4));
-    CUSZ_AMD_HIP_CHECK(hipMalloc(&d_brick_off, ((size_t)max_bricks + 1) * 4));
-    CUSZ_AMD_HIP_CHECK(hipMalloc(&d_spill, (size_t)spill_cap * 8));
-    CUSZ_AMD_HIP_CHECK(hipMalloc(&d_small, kSmallBytes));
+    CUSZ_AMD_HIP_CHECK(d_codes.alloc(code_len));
+    CUSZ_AMD_HIP_CHECK(d_hist.alloc(kMaxBklen + 4));  // + the sharded overflow word
+    CUSZ_AMD_HIP_CHECK(d_book.alloc(kMaxBklen));
+    CUSZ_AMD_HIP_CHECK(d_slots.alloc(slot_cells_total()));
+    CUSZ_AMD_HIP_CHECK(d_brick_cnt.alloc(max_bricks));
+    CUSZ_AMD_HIP_CHECK(d_brick_off.alloc((size_t)max_bricks + 1));
+    CUSZ_AMD_HIP_CHECK(d_spill.alloc(spill_cap));
+    CUSZ_AMD_HIP_CHECK(d_small.alloc(1));
     CUSZ_AMD_HIP_CHECK(hipMemset(d_small, 0, kSmallBytes));
     CUSZ_AMD_HIP_CHECK(alloc_chunk_state());
-    CUSZ_AMD_HIP_CHECK(hipHostMalloc(&h_xfer, kXferBytes, hipHostMallocMapped | hipHostMallocCoherent));
+    CUSZ_AMD_HIP_CHECK(hipHostMalloc(&h_xfer.p, kXferBytes, hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(h_xfer, 0, kXferBytes);
-    for (auto& e : ev) CUSZ_AMD_HIP_CHECK(hipEventCreate(&e));
+    for (auto& e : ev) CUSZ_AMD_HIP_CHECK(hipEventCreate(&e.e));
     if (bl.g.ok)  // pass 1's sample: strided histogram + the done counter
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_shist, ((size_t)kMaxBklen * kSampleBinStride + 16) * sizeof(uint32_t)));
+      CUSZ_AMD_HIP_CHECK(d_shist.alloc((size_t)kMaxBklen * kSampleBinStride + 16));
     if (const char* g = getenv("CUSZ_AMD_NO_GATE")) gate = atoi(g) == 0;
     return PSZ_SUCCESS;
   }
@@ -341,8 +378,8 @@ struct Pipeline {
       broken = true;
       return -1;
     }
-    (void)hipFree(d_spill);
-    d_spill = grown;
+    d_spill.free();
+    d_spill.p = grown;
     spill_cap = (uint32_t)cap;
     if (alloc_chunk_state() != hipSuccess) {
       broken = true;
@@ -370,8 +407,8 @@ struct Pipeline {
       broken = true;
       return -1;
     }
-    (void)hipFree(d_slots);
-    d_slots = grown;
+    d_slots.free();
+    d_slots.p = grown;
     if (alloc_chunk_state() != hipSuccess) {
       broken = true;
       return -1;
@@ -382,22 +419,22 @@ struct Pipeline {
 
   hipError_t alloc_chunk_state()
   {
-    if (d_status) (void)hipFree(d_status), d_status = nullptr;
-    if (d_enc_temp) (void)hipFree(d_enc_temp), d_enc_temp = nullptr;
+    d_status.free();
+    d_enc_temp.free();
     if (const size_t tw = hf_encode_temp_words(sublen, pardeg)) {
-      const hipError_t et = hipMalloc(&d_enc_temp, tw * 4);
+      const hipError_t et = d_enc_temp.alloc(tw);
       if (et != hipSuccess) return et;
     }
-    if (d_archive) (void)hipFree(d_archive), d_archive = nullptr;
+    d_archive.free();
     status_words = (size_t)hf_encode_groups(sublen, pardeg) + 1;
-    hipError_t e = hipMalloc(&d_status, status_words * 8);
+    hipError_t e = d_status.alloc(status_words);
     if (e != hipSuccess) return e;
     const size_t ol_cells = std::max(slot_cells_total(), (size_t)sgeom.ntiles * spl_cap);
     // chunk tables: the tuned chunking's, or the brick layout's (one chunk per brick row)
     const size_t chunks = std::max((size_t)pardeg, bl.g.ok ? (size_t)bl.g.nchunks : 0);
-    archive_cap = 176 + (size_t)elem_bytes * sgeom.anchor_len + 128 + rvbk_bytes(kMaxBklen) + 8 * chunks +
-                  4 * (bitstream_cells_cap() + chunks) + 8 * (ol_cells + spill_cap) + 64;
-    return hipMalloc(&d_archive, archive_cap);
+    const PhfLayout lay((size_t)elem_bytes * sgeom.anchor_len, kMaxBklen, chunks);
+    archive_cap = lay.phf_off + lay.bits_rel + 4 * (bitstream_cells_cap() + chunks) + 8 * (ol_cells + spill_cap) + 64;
+    return d_archive.alloc(archive_cap);
   }
 
   // device words -> host-mapped memory, then wait for the flag (fallback: stream sync)
@@ -443,6 +480,20 @@ struct Pipeline {
     return ms;
   }
 
+  // Rel mode: eb *= (max - min)  (libcusz.cc:287-293; range in double of T extrema)
+  template <typename T>
+  int scale_rel_eb(psz_header* h, const T* in)
+  {
+    if (h->rc.mode != Rel) return PSZ_SUCCESS;
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_extrema<T>(in, n, minmax(), ext_scratch(), stream));
+    if (int fs = fetch(regions({{h_readback()->minmax, minmax(), 16}}), 1)) return fs;
+    double mm[2];
+    std::memcpy(mm, h_readback()->minmax, 16);
+    h->min_val = mm[0], h->max_val = mm[1];
+    h->rc.eb *= (mm[1] - mm[0]);
+    return PSZ_SUCCESS;
+  }
+
   // state carried from compress_scan (pass 1) to compress_finish (codebook onwards)
   struct Pending {
     bool active = false, brick = false, spl = false, zz = false;
@@ -452,6 +503,66 @@ struct Pipeline {
     bool side_book = false;   // pass 1 publishes a codebook sample to the host (epoch: hist_epoch)
     size_t anchor_bytes = 0;
   } pend;
+
+  // The codebook's trip through the host: the histogram arrives with epoch eh (flag 2), the host
+  // builds the book, and -- when armed -- opens the gate (flag 5 = eg) that the launches queued
+  // behind the book poll on the device.  A local object of each compress path: a stream waiting on
+  // a gate that never opens hangs every later call on it, so the destructor opens an armed gate
+  // on every path out, the early error returns included.
+  struct BookGate {
+    Pipeline& p;
+    int bklen;
+    uint32_t eh = 0, eg = 0;
+    bool armed = false;
+    ~BookGate()
+    {
+      if (armed) __atomic_store_n(p.flag(5), eg, __ATOMIC_RELEASE);
+    }
+    // twoqueue: the two-queue book of histogram + 1 (a sample: every code encodable; codebook.cc),
+    // else the reference's heap on the full histogram
+    int build(bool twoqueue)
+    {
+      const int fs = p.wait_flag(2, eh);
+      if (!fs) {
+        if (twoqueue)
+          build_codebook_twoqueue(p.h_hist(), bklen, 1u, p.h_book(), p.h_revbook());
+        else
+          build_codebook(p.h_hist(), bklen, p.h_book(), p.h_revbook());
+      }
+      if (armed) __atomic_store_n(p.flag(5), eg, __ATOMIC_RELEASE);  // always open the gate
+      armed = false;
+      return fs;
+    }
+  };
+
+  // The codebook stage of compress_finish and compress_brick: book and reverse book (the latter
+  // into the archive) from the device histogram.  Host book: the histogram is published now unless
+  // pass 1 did, and the book is uploaded behind the gate, which g.build() opens once the caller
+  // has queued its remaining launches (g.armed) -- or, ungated (CUSZ_AMD_NO_GATE), built here and
+  // uploaded plainly.  Otherwise (spline, a sharded finish) the device book, no host round trip.
+  int book_stage(BookGate& g, bool twoqueue, const PhfLayout& lay)
+  {
+    uint8_t* revbook = d_archive + lay.phf_off + lay.rvbk_rel;
+    if (codebook != PSZ_AMD_CODEBOOK_EXACT && pend.hist_epoch == 0) {
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_book_device(d_hist, g.bklen, 0u, d_book, revbook, stream));
+      return PSZ_SUCCESS;
+    }
+    g.eh = pend.hist_epoch;  // published by pass 1's last workgroup, or now
+    if (!g.eh) {
+      g.eh = ++epoch;
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_publish(hist_regions(g.bklen), const_cast<uint32_t*>(flag(2)), g.eh, stream));
+    }
+    g.eg = ++gate_epoch;
+    g.armed = gate;
+    if (!g.armed)
+      if (int fs = g.build(twoqueue)) return fs;
+    const XferRegions up = regions({{d_book, h_book(), (size_t)g.bklen * 4}, {revbook, h_revbook(), lay.rvbk}});
+    if (g.armed)
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_gate_upload(up, const_cast<const uint32_t*>(flag(5)), g.eg, timeout(), stream));
+    else
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_upload(up, stream));
+    return PSZ_SUCCESS;
+  }
 
   template <typename T>
   int compress(psz_header* h, const T* in, uint8_t** out, size_t* outlen)
@@ -492,10 +603,10 @@ struct Pipeline {
     const bool spl = pred == Spline;
     if (spl && !d_spl_slots) {  // spline outlier slots: one range per 32x8x8 tile, allocated on first use
       spl_slot_cells = (size_t)sgeom.ntiles * spl_cap;
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_spl_slots, spl_slot_cells * 8));
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_spl_cnt, (size_t)sgeom.ntiles * 4));
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_spl_off, ((size_t)sgeom.ntiles + 1) * 4));
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_spl_sps, (size_t)sgeom.ntiles * 4));
+      CUSZ_AMD_HIP_CHECK(d_spl_slots.alloc(spl_slot_cells));
+      CUSZ_AMD_HIP_CHECK(d_spl_cnt.alloc(sgeom.ntiles));
+      CUSZ_AMD_HIP_CHECK(d_spl_off.alloc((size_t)sgeom.ntiles + 1));
+      CUSZ_AMD_HIP_CHECK(d_spl_sps.alloc(sgeom.ntiles));
     }
     const int radius = h->rc.radius;
     const int bklen = 2 * radius;
@@ -513,29 +624,15 @@ struct Pipeline {
     }
 
     mark(0);
-    // Rel mode: eb *= (max - min)  (libcusz.cc:287-293; range in double of T extrema)
-    if (h->rc.mode == Rel) {
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_extrema<T>(in, n, minmax(), ext_scratch(), stream));
-      int fs = fetch(regions({{h_readback() + 512, minmax(), 16}}), 1);
-      if (fs) return fs;
-      double mm[2];
-      std::memcpy(mm, h_readback() + 512, 16);
-      h->min_val = mm[0], h->max_val = mm[1];
-      h->rc.eb *= (mm[1] - mm[0]);
-    }
+    if (int fs = scale_rel_eb<T>(h, in)) return fs;
     const double eb = h->rc.eb;
 
-    // per-call state reset (the reference never resets these: SURVEY.md Appendix B.3)
-    if (brick)
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_zero(regions({{d_hist, nullptr, (size_t)(bklen + 1) * 4},
-                                                          {d_small, nullptr, kSmallZeroBytes},
-                                                          {d_shist, nullptr, ((size_t)kMaxBklen * kSampleBinStride + 16) * 4}}),
-                                                 stream));
-    else
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_zero(regions({{d_hist, nullptr, (size_t)(bklen + 1) * 4},
-                                                          {d_small, nullptr, kSmallZeroBytes},
-                                                          {d_status, nullptr, status_words * 8}}),
-                                                 stream));
+    // per-call state reset (the reference never resets these: SURVEY.md Appendix B.3); the third
+    // region: pass 1's codebook sample (bricks), else the encoder's look-back words
+    void* const z3 = brick ? (void*)d_shist.p : (void*)d_status.p;
+    const size_t z3_bytes = brick ? ((size_t)kMaxBklen * kSampleBinStride + 16) * 4 : status_words * 8;
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_zero(
+        regions({{d_hist, nullptr, (size_t)(bklen + 1) * 4}, {d_small, nullptr, kSmallZeroBytes}, {z3, nullptr, z3_bytes}}), stream));
     mark(1);
     last_layout = brick ? PSZ_AMD_LAYOUT_BRICK : PSZ_AMD_LAYOUT_REFERENCE;
     pend.brick = brick, pend.spl = spl, pend.radius = radius, pend.zz = zz;
@@ -635,62 +732,21 @@ struct Pipeline {
     // as in the brick path, every launch after the book is queued now behind a device-polled
     // gate, and the last kernel publishes the summary: the histogram's trip to the host overlaps
     // nothing, but no launch waits on the host's build.
-    const bool host_book = codebook == PSZ_AMD_CODEBOOK_EXACT || pend.hist_epoch != 0;
-    uint32_t eh = 0, eg = 0;
-    bool gated = false;
-    struct GateGuard {  // the gate opens on every path out of here (see compress_brick)
-      volatile uint32_t* f;
-      uint32_t e;
-      bool armed;
-      ~GateGuard()
-      {
-        if (armed) __atomic_store_n(f, e, __ATOMIC_RELEASE);
-      }
-    } guard{flag(5), 0, false};
-    auto build_book = [&]() -> int {
-      int fs = wait_flag(2, eh);
-      if (!fs) build_codebook(h_hist(), bklen, h_book(), h_revbook());
-      if (gated) __atomic_store_n(flag(5), eg, __ATOMIC_RELEASE);  // always open the gate
-      guard.armed = false;
-      return fs;
-    };
-    if (host_book) {
-      eh = pend.hist_epoch;  // published by the Lorenzo kernel's last workgroup, or now
-      if (!eh) {
-        eh = ++epoch;
-        CUSZ_AMD_HIP_CHECK((hipError_t)launch_publish(hist_regions(bklen), const_cast<uint32_t*>(flag(2)), eh, stream));
-      }
-      eg = ++gate_epoch;
-      gated = gate;
-      guard.e = eg, guard.armed = gated;
-      if (!gated)
-        if (int fs = build_book()) return fs;
-    }
-    const size_t phf_off = 176 + anchor_bytes;  // anchors: spline only (compressor.inl:160)
-    const size_t rvbk = rvbk_bytes(bklen);
-    const size_t nbit_rel = 128 + rvbk, entry_rel = nbit_rel + 4 * (size_t)pardeg;
-    const size_t bits_rel = entry_rel + 4 * (size_t)pardeg;
-    if (!host_book)
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_book_device(d_hist, bklen, 0u, d_book, d_archive + phf_off + 128, stream));
-    else {
-      const XferRegions up =
-          regions({{d_book, h_book(), (size_t)bklen * 4}, {d_archive + phf_off + 128, h_revbook(), rvbk}});
-      if (gated)
-        CUSZ_AMD_HIP_CHECK((hipError_t)launch_gate_upload(up, const_cast<const uint32_t*>(flag(5)), eg, timeout(), stream));
-      else
-        CUSZ_AMD_HIP_CHECK((hipError_t)launch_upload(up, stream));
-    }
+    const PhfLayout lay(anchor_bytes, bklen, (size_t)pardeg);
+    BookGate book{*this, bklen};
+    if (int fs = book_stage(book, false, lay)) return fs;
     mark(3);
 
+    uint8_t* phf = d_archive + lay.phf_off;
     HfEncodeArgs ea{d_codes,
                     n,
                     d_book,
                     bklen,
                     sublen,
                     pardeg,
-                    reinterpret_cast<uint32_t*>(d_archive + phf_off + nbit_rel),
-                    reinterpret_cast<uint32_t*>(d_archive + phf_off + entry_rel),
-                    reinterpret_cast<uint32_t*>(d_archive + phf_off + bits_rel),
+                    reinterpret_cast<uint32_t*>(phf + lay.nbit_rel),
+                    reinterpret_cast<uint32_t*>(phf + lay.entry_rel),
+                    reinterpret_cast<uint32_t*>(phf + lay.bits_rel),
                     d_status,
                     timeout(),
                     d_enc_temp};
@@ -701,21 +757,14 @@ struct Pipeline {
 
     // header templates: static fields from the host, dynamic ones filled on the device (by the
     // finalize workgroup, which knows the totals)
-    h->vle_sublen = sublen;
-    h->vle_pardeg = pardeg;
-    h->len = len;
-    h->entry[0] = 0, h->entry[1] = 176, h->entry[2] = (uint32_t)phf_off;
     phf_header ph;
-    std::memset(&ph, 0, sizeof(ph));
-    ph.bklen = bklen, ph.sublen = sublen, ph.pardeg = pardeg, ph.original_len = n;
-    ph.entry[0] = 0, ph.entry[1] = 128, ph.entry[2] = (uint32_t)nbit_rel, ph.entry[3] = (uint32_t)entry_rel;
-    ph.entry[4] = (uint32_t)bits_rel;
+    fill_header_templates(lay, bklen, sublen, pardeg, n, len, h, &ph);
     FinalizeArgs fa{ea.par_nbit, ea.par_entry, pardeg, bcnt, nbr, cap, spill_cnt(), spill_cap, boff, info(),
                     spill_start};
     fa.nbit_known = true;
-    CUSZ_AMD_HIP_CHECK((hipError_t)launch_finalize_scan(fa, stream, h, &ph, d_archive, phf_off, bits_rel));
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_finalize_scan(fa, stream, h, &ph, d_archive, lay.phf_off, lay.bits_rel));
     OutlierCopyArgs oa{slots, bcnt,      boff,           nbr, cap, d_spill, spill_cnt(), spill_cap,
-                       info(), d_archive, phf_off + bits_rel, spill_start};
+                       info(), d_archive, lay.phf_off + lay.bits_rel, spill_start};
     // the copy's last workgroup publishes the summary finish_compress reads (no publish launch)
     // when its grid is small; a large grid pays the publish per block, so a publish launch follows
     const HostPub sp{readback_regions(), const_cast<uint32_t*>(flag(3)), ++epoch, summary_ticket()};
@@ -725,8 +774,8 @@ struct Pipeline {
       CUSZ_AMD_HIP_CHECK((hipError_t)launch_publish(sp.r, sp.flag, sp.epoch, stream));
     summary_epoch = sp.epoch;
     mark(5);
-    if (gated)
-      if (int fs = build_book()) return fs;
+    if (book.armed)
+      if (int fs = book.build(false)) return fs;
     return finish_compress(h, out, outlen);
   }
 
@@ -747,85 +796,29 @@ struct Pipeline {
     // launch after the codebook is queued NOW: the upload kernel polls a host-mapped gate word the
     // host sets once the book is built, so the encode kernels start right after it instead of
     // after the host's launch latency (and without the command processor's stream-wait latency).
-    const size_t phf_off = 176;
-    const size_t rvbk = rvbk_bytes(bklen);
-    const size_t nbit_rel = 128 + rvbk, entry_rel = nbit_rel + 4 * (size_t)bpar;
-    const size_t bits_rel = entry_rel + 4 * (size_t)bpar;
+    const PhfLayout lay(0, bklen, (size_t)bpar);
     // host book: the reference heap on the full histogram (EXACT; 2-D bricks) or the two-queue
-    // book of pass 1's sample + 1 (SAMPLED, published mid-pass); otherwise (a sharded finish) the
-    // device book
+    // book of pass 1's sample + 1 (SAMPLED, published mid-pass); otherwise (a sharded finish: every
+    // rank holds the same reduced histogram) the device book
     const bool sampled = pend.side_book;
-    const bool host_book = codebook == PSZ_AMD_CODEBOOK_EXACT || pend.hist_epoch != 0;
     pend.side_book = false;
-    uint32_t eh = 0, eg = 0;
-    bool gated = false;
-    // the gate must open on every path out of here, or the stream (and every later call on
-    // it) waits forever: an early error return before build_book() opens it in the destructor
-    struct GateGuard {
-      volatile uint32_t* f;
-      uint32_t e;
-      bool armed;
-      ~GateGuard()
-      {
-        if (armed) __atomic_store_n(f, e, __ATOMIC_RELEASE);
-      }
-    } guard{flag(5), 0, false};
-    auto build_book = [&]() -> int {
-      int fs = wait_flag(2, eh);
-      if (!fs) {
-        if (sampled)  // two-queue book of sample + 1 (every code encodable; codebook.cc)
-          build_codebook_twoqueue(h_hist(), bklen, 1u, h_book(), h_revbook());
-        else
-          build_codebook(h_hist(), bklen, h_book(), h_revbook());
-      }
-      if (gated) __atomic_store_n(flag(5), eg, __ATOMIC_RELEASE);  // always open the gate
-      guard.armed = false;
-      return fs;
-    };
-    if (!host_book) {
-      // device codebook, no host round trip (a sharded finish: every rank holds the same reduced
-      // histogram): built now from the full histogram
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_book_device(d_hist, bklen, 0u, d_book, d_archive + phf_off + 128, stream));
-    }
-    else {
-      eh = pend.hist_epoch;  // published by the scan's last workgroup, or now
-      if (!eh) {
-        eh = ++epoch;
-        CUSZ_AMD_HIP_CHECK((hipError_t)launch_publish(hist_regions(bklen), const_cast<uint32_t*>(flag(2)), eh, stream));
-      }
-      eg = ++gate_epoch;
-      gated = gate;
-      guard.e = eg, guard.armed = gated;
-      if (!gated)
-        if (int fs = build_book()) return fs;
-      const XferRegions up =
-          regions({{d_book, h_book(), (size_t)bklen * 4}, {d_archive + phf_off + 128, h_revbook(), rvbk}});
-      if (gated)
-        CUSZ_AMD_HIP_CHECK((hipError_t)launch_gate_upload(up, const_cast<const uint32_t*>(flag(5)), eg, timeout(), stream));
-      else
-        CUSZ_AMD_HIP_CHECK((hipError_t)launch_upload(up, stream));
-    }
+    BookGate book{*this, bklen};
+    if (int fs = book_stage(book, sampled, lay)) return fs;
     mark(3);
 
-    uint32_t* par_nbit = reinterpret_cast<uint32_t*>(d_archive + phf_off + nbit_rel);
-    uint32_t* par_entry = reinterpret_cast<uint32_t*>(d_archive + phf_off + entry_rel);
-    uint32_t* bits = reinterpret_cast<uint32_t*>(d_archive + phf_off + bits_rel);
+    uint8_t* phf = d_archive + lay.phf_off;
+    uint32_t* par_nbit = reinterpret_cast<uint32_t*>(phf + lay.nbit_rel);
+    uint32_t* par_entry = reinterpret_cast<uint32_t*>(phf + lay.entry_rel);
+    uint32_t* bits = reinterpret_cast<uint32_t*>(phf + lay.bits_rel);
 
     // header templates: static fields from the host, sizes filled by the plan kernel
-    h->vle_sublen = bsub;
-    h->vle_pardeg = bpar;
-    h->len = len;
-    h->entry[0] = 0, h->entry[1] = 176, h->entry[2] = (uint32_t)phf_off;
     phf_header ph;
-    std::memset(&ph, 0, sizeof(ph));
-    ph.bklen = bklen, ph.sublen = bsub, ph.pardeg = bpar, ph.original_len = n;
-    ph.entry[0] = 0, ph.entry[1] = 128, ph.entry[2] = (uint32_t)nbit_rel, ph.entry[3] = (uint32_t)entry_rel;
-    ph.entry[4] = (uint32_t)bits_rel;
+    fill_header_templates(lay, bklen, bsub, bpar, n, len, h, &ph);
 
     const uint32_t nblk = brick_plan_blocks(g.nbricks);
     BrickPlanArgs pa{d_bhist, bklen, brick_hist_stride(bklen), d_book, g.nbricks, brick_units(g.nbricks), g.nbx, g.nby, bl.ly, bl.lz,
                      d_brick_cnt, cap, d_slots, d_spill, spill_cnt(), spill_cap, nblk, d_ub, d_bbase, d_brick_off,
-                     d_plan, d_plan + nblk + 1, info(), d_archive, phf_off, bits_rel};
+                     d_plan, d_plan + nblk + 1, info(), d_archive, lay.phf_off, lay.bits_rel};
     pa.nd = g.ndim == 3 ? 3u : 1u, pa.nchunks = g.nchunks, pa.n = g.n;  // 1-D and 2-D: linear bricks
     pa.ticket = plan_ticket();
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_plan(bl, pa, h, &ph, stream));
@@ -835,8 +828,8 @@ struct Pipeline {
                                                      pack_reverse, timeout(), stream, sp));
     summary_epoch = sp.epoch;
     mark(4);
-    if (gated)
-      if (int fs = build_book()) return fs;
+    if (book.armed)
+      if (int fs = book.build(sampled)) return fs;
     mark(5);
     return finish_compress(h, out, outlen);
   }
@@ -859,19 +852,11 @@ struct Pipeline {
     if (radius < 1 || bklen > kMaxBklen) return PSZ_AMD_ERR_INVALID_ARG;
     const BrickGeom& g = bl.g;
     mark(0);
-    if (h->rc.mode == Rel) {  // libcusz.cc:287-293
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_extrema<T>(in, n, minmax(), ext_scratch(), stream));
-      int fs = fetch(regions({{h_readback() + 512, minmax(), 16}}), 1);
-      if (fs) return fs;
-      double mm[2];
-      std::memcpy(mm, h_readback() + 512, 16);
-      h->min_val = mm[0], h->max_val = mm[1];
-      h->rc.eb *= (mm[1] - mm[0]);
-    }
+    if (int fs = scale_rel_eb<T>(h, in)) return fs;
     const double eb = h->rc.eb;
     // the look-back status words (one per brick), then the outlier count and destination of each
     // (brick, y-step) slot, live in the per-brick histogram area (unused in this mode: 2 KB a brick)
-    unsigned long long* status = reinterpret_cast<unsigned long long*>(d_bhist);
+    unsigned long long* status = reinterpret_cast<unsigned long long*>(d_bhist.p);
     uint32_t* slot_cnt = reinterpret_cast<uint32_t*>(status + g.nbricks);
     uint32_t* slot_dst = slot_cnt + (size_t)g.nbricks * kStreamSlots;
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_zero(regions({{d_shist, nullptr, (size_t)kMaxBklen * kSampleBinStride * 4},
@@ -880,54 +865,31 @@ struct Pipeline {
                                                stream));
     mark(1);
     last_layout = PSZ_AMD_LAYOUT_BRICK;
-    const size_t phf_off = 176;
-    const size_t rvbk = rvbk_bytes(bklen);
     const int bsub = g.W, bpar = (int)g.nchunks;
-    const size_t nbit_rel = 128 + rvbk, entry_rel = nbit_rel + 4 * (size_t)bpar;
-    const size_t bits_rel = entry_rel + 4 * (size_t)bpar;
+    const PhfLayout lay(0, bklen, (size_t)bpar);
+    // the host's two-queue book of sample + 1 opens the gate the streaming pass polls (always
+    // armed: CUSZ_AMD_NO_GATE only moves the build before the launch)
+    BookGate book{*this, bklen};
     // the sample histogram; its last workgroup publishes it to the host (flag 2)
-    const uint32_t eh = ++epoch;
+    book.eh = ++epoch;
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_sample<T>(bl, in, eb, radius, zz, d_shist, bklen, hist_ticket(), h_hist(),
-                                                          const_cast<uint32_t*>(flag(2)), eh, stream));
+                                                          const_cast<uint32_t*>(flag(2)), book.eh, stream));
     mark(2);
-    // the host's two-queue book of sample + 1 opens the gate the streaming pass polls; it must
-    // open on every path out of here, or the stream (and every later call on it) waits forever
-    const uint32_t eg = ++gate_epoch;
-    struct GateGuard {
-      volatile uint32_t* f;
-      uint32_t e;
-      bool armed;
-      ~GateGuard()
-      {
-        if (armed) __atomic_store_n(f, e, __ATOMIC_RELEASE);
-      }
-    } guard{flag(5), eg, true};
-    auto build_book = [&]() -> int {
-      int fs = wait_flag(2, eh);
-      if (!fs) build_codebook_twoqueue(h_hist(), bklen, 1u, h_book(), h_revbook());
-      __atomic_store_n(flag(5), eg, __ATOMIC_RELEASE);
-      guard.armed = false;
-      return fs;
-    };
+    book.eg = ++gate_epoch;
+    book.armed = true;
     if (!gate)  // (diagnostic switch: the book before the launch)
-      if (int fs = build_book()) return fs;
+      if (int fs = book.build(true)) return fs;
     mark(3);
-    h->vle_sublen = bsub;
-    h->vle_pardeg = bpar;
-    h->len = len;
-    h->entry[0] = 0, h->entry[1] = 176, h->entry[2] = (uint32_t)phf_off;
     phf_header ph;
-    std::memset(&ph, 0, sizeof(ph));
-    ph.bklen = bklen, ph.sublen = bsub, ph.pardeg = bpar, ph.original_len = n;
-    ph.entry[0] = 0, ph.entry[1] = 128, ph.entry[2] = (uint32_t)nbit_rel, ph.entry[3] = (uint32_t)entry_rel;
-    ph.entry[4] = (uint32_t)bits_rel;
+    fill_header_templates(lay, bklen, bsub, bpar, n, len, h, &ph);
+    uint8_t* phf = d_archive + lay.phf_off;
     const size_t chunks = std::max((size_t)pardeg, (size_t)g.nchunks);
     BrickSingle sg{OutlierSink{d_slots, slot_cnt, d_spill, spill_cnt(), brick_cap() / kStreamSlots, spill_cap, nullptr},
                    d_book,
                    bklen,
-                   reinterpret_cast<uint32_t*>(d_archive + phf_off + nbit_rel),
-                   reinterpret_cast<uint32_t*>(d_archive + phf_off + entry_rel),
-                   reinterpret_cast<uint32_t*>(d_archive + phf_off + bits_rel),
+                   reinterpret_cast<uint32_t*>(phf + lay.nbit_rel),
+                   reinterpret_cast<uint32_t*>(phf + lay.entry_rel),
+                   reinterpret_cast<uint32_t*>(phf + lay.bits_rel),
                    (uint32_t)std::min<size_t>(bitstream_cells_cap() + chunks, 0xFFFFFFFFu),
                    status,
                    &info()->ticket,
@@ -935,22 +897,22 @@ struct Pipeline {
                    info(),
                    timeout(),
                    d_archive,
-                   phf_off,
-                   bits_rel,
+                   lay.phf_off,
+                   lay.bits_rel,
                    const_cast<const uint32_t*>(flag(5)),
-                   eg,
+                   book.eg,
                    h_book(),
                    reinterpret_cast<const uint32_t*>(h_revbook()),
-                   reinterpret_cast<uint32_t*>(d_archive + phf_off + 128),
-                   (int)(rvbk / 4),
+                   reinterpret_cast<uint32_t*>(phf + lay.rvbk_rel),
+                   (int)(lay.rvbk / 4),
                    book_flag()};
     const HostPub sp{readback_regions(), const_cast<uint32_t*>(flag(3)), ++epoch, summary_ticket()};
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_stream<T>(bl, in, eb, radius, zz, sg, h, &ph, stream, sp));
     summary_epoch = sp.epoch;
     mark(4);
     mark(5);
-    if (guard.armed)
-      if (int fs = build_book()) return fs;
+    if (book.armed)
+      if (int fs = book.build(true)) return fs;
     return finish_compress(h, out, outlen);
   }
 
@@ -958,23 +920,24 @@ struct Pipeline {
   // the histogram for the host codebook, and with a caller's reduced histogram its overflow word
   XferRegions hist_regions(int bklen)
   {
-    if (pend.ext) return regions({{h_hist(), d_hist, (size_t)bklen * 4}, {h_readback() + 448, d_hist + bklen, 4}});
+    if (pend.ext) return regions({{h_hist(), d_hist, (size_t)bklen * 4}, {&h_readback()->excess, d_hist + bklen, 4}});
     return regions({{h_hist(), d_hist, (size_t)bklen * 4}});
   }
-  uint32_t global_excess() const { return pend.ext ? *reinterpret_cast<const uint32_t*>(h_readback() + 448) : 0u; }
+  uint32_t global_excess() const { return pend.ext ? h_readback()->excess : 0u; }
 
   XferRegions readback_regions()
   {
     // a sharded finish also reads back the summed overflow word (the device-book path sends no
     // histogram to the host)
+    Readback* rb = h_readback();
     if (pend.ext)
-      return regions({{h_readback(), d_archive, 176},
-                      {h_readback() + 256, info(), sizeof(CompressInfo)},
-                      {h_readback() + 384, timeout(), 4},
-                      {h_readback() + 448, d_hist + 2 * pend.radius, 4}});
-    return regions({{h_readback(), d_archive, 176},
-                    {h_readback() + 256, info(), sizeof(CompressInfo)},
-                    {h_readback() + 384, timeout(), 4}});
+      return regions({{rb->header, d_archive, sizeof(psz_header)},
+                      {&rb->info, info(), sizeof(CompressInfo)},
+                      {&rb->timeout, timeout(), 4},
+                      {&rb->excess, d_hist + 2 * pend.radius, 4}});
+    return regions({{rb->header, d_archive, sizeof(psz_header)},
+                    {&rb->info, info(), sizeof(CompressInfo)},
+                    {&rb->timeout, timeout(), 4}});
   }
 
   int finish_compress(psz_header* h, uint8_t** out, size_t* outlen)
@@ -984,11 +947,12 @@ struct Pipeline {
     int fs = se ? wait_flag(3, se) : fetch(readback_regions(), 3);
     if (fs) return fs;
     if (timing) CUSZ_AMD_HIP_CHECK(hipEventSynchronize(ev[5]));
+    const Readback* rb = h_readback();
     CompressInfo ci;
-    std::memcpy(&ci, h_readback() + 256, sizeof(ci));
+    std::memcpy(&ci, &rb->info, sizeof(ci));
     unsigned int tmo;
-    std::memcpy(&tmo, h_readback() + 384, 4);
-    std::memcpy(h, h_readback(), 176);
+    std::memcpy(&tmo, &rb->timeout, 4);
+    std::memcpy(h, rb->header, sizeof(psz_header));
     splen = (size_t)ci.splen;
     if (timing) {
       stage_ms[PSZ_AMD_T_EXTREMA] = span(0, 1);
@@ -1032,37 +996,17 @@ struct Pipeline {
   {
     // the decoders write d_codes, which a pending compress_finish would pack (as decompress)
     pend.active = false;
-    const int bklen = 2 * h->rc.radius;
-    const size_t phf_off = h->entry[PSZHEADER_ENCODED];
-    const size_t rvbk = rvbk_bytes(bklen);
-    const int pd = h->vle_pardeg, sl = h->vle_sublen;
-    const uint8_t* phf = in + phf_off;
-    if (sl % 64 == 0 && sl <= 8192 && decoder == 0 && pd > 0 && bklen <= kMaxBklen) {  // the fused decoders' chunk loop
-      const size_t bits_off = phf_off + 128 + rvbk + 8 * (size_t)pd;
-      const size_t total = h->entry[PSZHEADER_ENC_PASS2_END];
-      const size_t bs_words = total > bits_off ? (total - bits_off) / 4 : 0;
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_chunk_decode(
-          bl, reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 8 * (size_t)pd), bs_words, phf + 128, bklen,
-          reinterpret_cast<const uint32_t*>(phf + 128 + rvbk), reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 4 * (size_t)pd),
-          d_codes, n, (uint32_t)pd, (uint32_t)sl, stream));
+    const PhfView v(h, in);
+    const int pd = v.pardeg, sl = v.sublen;
+    if (sl % 64 == 0 && sl <= 8192 && decoder == 0 && pd > 0 && v.bklen <= kMaxBklen) {  // the fused decoders' chunk loop
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_chunk_decode(bl, v, d_codes, n, stream));
       return PSZ_SUCCESS;
     }
-    HfDecodeArgs da{reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 8 * (size_t)pd),
-                    phf + 128,
-                    bklen,
-                    reinterpret_cast<const uint32_t*>(phf + 128 + rvbk),
-                    reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 4 * (size_t)pd),
-                    sl,
-                    pd,
-                    n,
-                    d_codes,
-                    dec_lut(),
-                    0,
-                    decoder};
     // average chunk size from the segment length (sizes the decoder's LDS staging)
     const size_t seg = h->entry[PSZHEADER_ENCODED + 1] - h->entry[PSZHEADER_ENCODED];
-    const size_t fixed = 128 + rvbk + 8 * (size_t)pd;
-    if (pd > 0 && seg > fixed) da.avg_cells = (seg - fixed) / 4 / (size_t)pd;
+    const size_t avg_cells = pd > 0 && seg > v.bits_rel ? (seg - v.bits_rel) / 4 / (size_t)pd : 0;
+    const HfDecodeArgs da{v.bitstream, v.revbook, v.bklen, v.par_nbit, v.par_entry, sl,
+                          pd,          n,         d_codes, dec_lut(),  avg_cells,   decoder};
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_hf_decode(da, stream));
     return PSZ_SUCCESS;
   }
@@ -1123,19 +1067,7 @@ struct Pipeline {
   template <typename T>
   int decompress_brick(const psz_header* h, const uint8_t* in, T* out, bool zz, const BrickOutliers& bo)
   {
-    const int bklen = 2 * h->rc.radius;
-    const size_t phf_off = h->entry[PSZHEADER_ENCODED];
-    const size_t rvbk = rvbk_bytes(bklen);
-    const int pd = h->vle_pardeg;
-    const uint8_t* phf = in + phf_off;
-    // words from the bitstream start to the end of the archive (range of the decoder's loads)
-    const size_t bits_off = phf_off + 128 + rvbk + 8 * (size_t)pd;
-    const size_t total = h->entry[PSZHEADER_ENC_PASS2_END];
-    const size_t bs_words = total > bits_off ? (total - bits_off) / 4 : 0;
-    CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_decode<T>(
-        bl, reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 8 * (size_t)pd), bs_words, phf + 128, bklen,
-        reinterpret_cast<const uint32_t*>(phf + 128 + rvbk), reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 4 * (size_t)pd),
-        out, h->rc.eb, h->rc.radius, zz, bo, stream));
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_decode<T>(bl, PhfView(h, in), out, h->rc.eb, h->rc.radius, zz, bo, stream));
     mark(8);
     mark(9);
     return PSZ_SUCCESS;
@@ -1169,25 +1101,16 @@ struct Pipeline {
       bo = BrickOutliers{cells, (size_t)h->splen, d_x1d, d_x1d + nb + 1, cell_epoch};
     }
     if (fused) {
-      const int bklen = 2 * h->rc.radius;
-      const size_t phf_off = h->entry[PSZHEADER_ENCODED];
-      const size_t rvbk = rvbk_bytes(bklen);
-      const int pd = h->vle_pardeg;  // (== bl.g.nchunks: region_plan)
-      const uint8_t* phf = in + phf_off;
-      const size_t bits_off = phf_off + 128 + rvbk + 8 * (size_t)pd;
-      const size_t total = h->entry[PSZHEADER_ENC_PASS2_END];
-      const size_t bs_words = total > bits_off ? (total - bits_off) / 4 : 0;
+      // (vle_pardeg == bl.g.nchunks: region_plan)
       const uint32_t o3[3] = {(uint32_t)o.x, (uint32_t)o.y, (uint32_t)o.z}, e3[3] = {(uint32_t)e.x, (uint32_t)e.y, (uint32_t)e.z};
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_region<T>(
-          bl, reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 8 * (size_t)pd), bs_words, phf + 128, bklen,
-          reinterpret_cast<const uint32_t*>(phf + 128 + rvbk), reinterpret_cast<const uint32_t*>(phf + 128 + rvbk + 4 * (size_t)pd),
-          out, h->rc.eb, h->rc.radius, bo, o3, e3, stream));
+      CUSZ_AMD_HIP_CHECK(
+          (hipError_t)launch_brick_region<T>(bl, PhfView(h, in), out, h->rc.eb, h->rc.radius, bo, o3, e3, stream));
     }
     else {
-      if (!d_region_field) CUSZ_AMD_HIP_CHECK(hipMalloc(&d_region_field, n * sizeof(T)));
-      if (const int s = decompress<T>(h, in, static_cast<T*>(d_region_field))) return s;
+      if (!d_region_field) CUSZ_AMD_HIP_CHECK(d_region_field.alloc(n * sizeof(T)));
+      if (const int s = decompress<T>(h, in, reinterpret_cast<T*>(d_region_field.p))) return s;
       const size_t o3[3] = {o.x, o.y, o.z}, e3[3] = {e.x, e.y, e.z};
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_crop_box<T>(static_cast<const T*>(d_region_field), len.x, len.y, o3, e3, out, stream));
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_crop_box<T>(reinterpret_cast<const T*>(d_region_field.p), len.x, len.y, o3, e3, out, stream));
       const size_t elems = info.elems;
       info = psz_amd_region_info{};
       info.path = PSZ_AMD_REGION_FALLBACK, info.elems = elems;
@@ -1205,8 +1128,7 @@ struct Pipeline {
     mark(6);
     const size_t words = spline_x_scratch_words(sgeom.ntiles, h->splen);
     if (words > spl_x_words) {
-      if (d_spl_x) (void)hipFree(d_spl_x), d_spl_x = nullptr;
-      CUSZ_AMD_HIP_CHECK(hipMalloc(&d_spl_x, words * 4));
+      CUSZ_AMD_HIP_CHECK(d_spl_x.alloc(words));
       spl_x_words = words;
     }
     mark(7);

@@ -18,7 +18,8 @@ def main():
     src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "cusz_amd", "csrc", "codebook.cc")
     d = tempfile.mkdtemp()
     so = os.path.join(d, "libcb.so")
-    subprocess.run(["g++", "-O3", "-std=c++17", "-shared", "-fPIC", "-o", so,
+    subprocess.run(["g++", "-O3", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"),
+                    "-I", os.path.join(ROOT, "cusz_amd", "csrc"), "-o", so,
                     os.path.join(ROOT, "tests", "host", "codebook_shim.cc"), src], check=True)
     lib = C.CDLL(so)
     lib.shim_build_codebook.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

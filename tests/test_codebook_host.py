@@ -18,7 +18,8 @@ def shim(tmp_path_factory):
     out = tmp_path_factory.mktemp("cb") / "libcbshim.so"
     src = [os.path.join(ROOT, "tests", "host", "codebook_shim.cc"), os.path.join(ROOT, "cusz_amd", "csrc", "codebook.cc")]
     try:
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(out)] + src, check=True,
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"),
+                        "-o", str(out)] + src, check=True,
                        capture_output=True, timeout=120)
     except (OSError, subprocess.CalledProcessError) as e:
         pytest.skip(f"g++ unavailable: {e}")
