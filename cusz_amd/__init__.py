@@ -39,8 +39,9 @@ STATUS_NAMES = [
 # extensions beyond psz_error_status (include/cusz_amd.h)
 PSZ_AMD_ERR_INVALID_ARG, PSZ_AMD_ERR_BAD_ARCHIVE, PSZ_AMD_ERR_DEVICE, PSZ_AMD_ERR_STATE, PSZ_AMD_ERR_ENCODER = (
     100, 101, 102, 103, 104)
+PSZ_AMD_ERR_CODE_RANGE = 105  # spline: a code the archive's outlier cells cannot carry
 EXT_STATUS_NAMES = {100: "PSZ_AMD_ERR_INVALID_ARG", 101: "PSZ_AMD_ERR_BAD_ARCHIVE", 102: "PSZ_AMD_ERR_DEVICE",
-                    103: "PSZ_AMD_ERR_STATE", 104: "PSZ_AMD_ERR_ENCODER"}
+                    103: "PSZ_AMD_ERR_STATE", 104: "PSZ_AMD_ERR_ENCODER", 105: "PSZ_AMD_ERR_CODE_RANGE"}
 
 T_EXTREMA, T_PREDICT, T_BOOK, T_ENCODE, T_FINALIZE, T_COMPRESS = range(6)
 T_SCATTER, T_DECODE, T_RECON, T_DECOMPRESS, T_COUNT = 6, 7, 8, 9, 10

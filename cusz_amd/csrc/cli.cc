@@ -204,7 +204,10 @@ int main(int argc, char** argv)
                            : psz_compress_double(m, rc, (double*)d_in, &out_h, &d_arch, &bytes);
     double wall = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
     if (s != PSZ_SUCCESS && s != PSZ_WARN_RADIUS_TOO_LARGE) {
-      std::fprintf(stderr, "[cusz] compress failed with status %d\n", s);
+      if (s == PSZ_AMD_ERR_CODE_RANGE)
+        std::fprintf(stderr, "[cusz] spline: |error|/(2*eb) beyond 2^24 (f64) / 2^31; use a larger bound or Lorenzo\n");
+      else
+        std::fprintf(stderr, "[cusz] compress failed with status %d\n", s);
       return 1;
     }
     std::vector<char> arch(bytes);

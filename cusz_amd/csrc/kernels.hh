@@ -175,6 +175,7 @@ struct SplineArgs {
   T* anchor;      // anchor_len values (written into the archive's anchor segment)
   OutlierSink ol; // one slot range per tile (cap_per_brick), spill list beyond
   uint32_t* hist;
+  uint32_t* code_lost;  // set when an outlier cell cannot carry its code (zeroed per call)
 };
 template <typename T>
 int launch_spline3_c(const SplineArgs<T>& a, hipStream_t st);

@@ -134,7 +134,7 @@ struct Event {  // likewise
 // of every compress; the tickets are the 9-word publish tickets of pub_device.hh.
 struct SmallBuf {
   uint32_t spill_cnt, pad0[3];
-  unsigned int timeout, pad1[11];
+  unsigned int timeout, code_lost, pad1[10];  // code_lost: spline codes no outlier cell can carry
   CompressInfo info;
   uint32_t plan_ticket[9], pad2[3];
   uint32_t hist_ticket[9];
@@ -149,7 +149,8 @@ struct SmallBuf {
 };
 constexpr size_t kSmallBytes = sizeof(SmallBuf);
 constexpr size_t kSmallZeroBytes = offsetof(SmallBuf, summary_ticket) + sizeof(SmallBuf::summary_ticket);
-static_assert(offsetof(SmallBuf, spill_cnt) == 0 && offsetof(SmallBuf, timeout) == 16 && offsetof(SmallBuf, info) == 64 &&
+static_assert(offsetof(SmallBuf, spill_cnt) == 0 && offsetof(SmallBuf, timeout) == 16 && offsetof(SmallBuf, code_lost) == 20 &&
+                  offsetof(SmallBuf, info) == 64 &&
                   offsetof(SmallBuf, plan_ticket) == 112 && offsetof(SmallBuf, hist_ticket) == 160 &&
                   offsetof(SmallBuf, summary_ticket) == 196 && offsetof(SmallBuf, book_flag) == 240 &&
                   offsetof(SmallBuf, minmax) == 256 && offsetof(SmallBuf, ext_scratch) == 512 &&
@@ -163,11 +164,12 @@ struct Readback {
   uint8_t header[sizeof(psz_header)], pad0[80];  // the archive's psz header
   CompressInfo info;
   uint8_t pad1[80];
-  unsigned int timeout, pad2[15];
+  unsigned int timeout, code_lost, pad2[14];  // read back together (SmallBuf keeps them adjacent)
   uint32_t excess, pad3[15];  // a sharded finish's summed overflow word
   double minmax[2];           // Rel mode's extrema
 };
 static_assert(offsetof(Readback, header) == 0 && offsetof(Readback, info) == 256 && offsetof(Readback, timeout) == 384 &&
+                  offsetof(Readback, code_lost) == 388 &&
                   offsetof(Readback, excess) == 448 && offsetof(Readback, minmax) == 512 && sizeof(Readback) <= 1024,
               "read-back layout");
 
@@ -682,7 +684,8 @@ struct Pipeline {
                        d_codes,
                        reinterpret_cast<T*>(d_archive + 176),
                        ol,
-                       d_hist};
+                       d_hist,
+                       &d_small.p->code_lost};
       pend.hist_epoch = 0;  // compress_finish publishes the histogram itself
       CUSZ_AMD_HIP_CHECK((hipError_t)launch_spline3_c<T>(sa, stream));
     }
@@ -933,11 +936,11 @@ struct Pipeline {
     if (pend.ext)
       return regions({{rb->header, d_archive, sizeof(psz_header)},
                       {&rb->info, info(), sizeof(CompressInfo)},
-                      {&rb->timeout, timeout(), 4},
+                      {&rb->timeout, timeout(), 8},
                       {&rb->excess, d_hist + 2 * pend.radius, 4}});
     return regions({{rb->header, d_archive, sizeof(psz_header)},
                     {&rb->info, info(), sizeof(CompressInfo)},
-                    {&rb->timeout, timeout(), 4}});
+                    {&rb->timeout, timeout(), 8}});
   }
 
   int finish_compress(psz_header* h, uint8_t** out, size_t* outlen)
@@ -966,6 +969,9 @@ struct Pipeline {
       std::fprintf(stderr, "[cusz_amd] encoder reservation/look-back check failed\n");
       return PSZ_AMD_ERR_ENCODER;
     }
+    // spline: some point's code is past what an outlier cell carries (cusz_amd.h): decompression
+    // could not reproduce the compressor's codes, so no archive is handed back
+    if (pend.spl && rb->code_lost) return PSZ_AMD_ERR_CODE_RANGE;
     if (ci.spilled && !pend.spl) {
       // bricks spilled past their slots: grow the slots to the largest brick's count so that the
       // repeat writes every cell in its brick's slot (deterministic order, fused decoders' ranked

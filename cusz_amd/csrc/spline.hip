@@ -36,6 +36,14 @@ constexpr int kPer = (kSN + kSplThreads - 1) / kSplThreads;  // scratch points p
 
 __device__ __forceinline__ int sidx(int x, int y, int z) { return x + kSX * (y + kSY * z); }
 
+// The code domain.  |code / 2| < kSplCodeLim = 2^31 - 1024, so that adding a radius of at most 512
+// stays an int (the conversion of a larger value saturates at the ends of int, which the limit
+// covers).  An outlier cell carries its code as a float (sp_interface.h), which holds every int
+// up to 2^24: the f64 compressor predicts on from the exact code, so a code the float rounds is
+// lost as well.  (f32 is consistent up to the limit: both sides compute with the float-rounded
+// code.)  Checked on the outlier path only: a code past the limit is never a kept one.
+constexpr int kSplCodeLim = 2147482624;
+
 // a value the compiler cannot treat as loop-invariant: the prefetch's per-point coordinates are
 // then recomputed at each fetch instead of living in ~40 extra VGPRs across the whole tile loop
 __device__ __forceinline__ int opaque(int v)
@@ -100,7 +108,9 @@ __device__ __forceinline__ void spl_stage(T* s, int* e, const TileInfo& t, float
       const T err = s[i] - pred;
       T code = (sizeof(T) == 4 ? (T)__builtin_fabsf((float)err) : (T)__builtin_fabs((double)err)) * (T)eb_r + 1;
       code = err < 0 ? -code : code;
-      const int ci = (int)(code / 2) + radius;
+      // (the conversion saturates past int, and the sum may wrap: the outlier pass of k_spline3_c
+      // undoes the sum and refuses such a field, PSZ_AMD_ERR_CODE_RANGE)
+      const int ci = (int)((uint32_t)(int)(code / 2) + (uint32_t)radius);
       e[i] = ci;
       s[i] = pred + ((T)ci - radius) * (T)ebx2;
     }
@@ -196,8 +206,10 @@ __global__ void __launch_bounds__(kSplThreads, 4) k_spline3_c(SplineArgs<T> a)
   __shared__ uint32_t s_hist[kMaxBklen];
   __shared__ uint32_t s_pc[8][4];  // outliers per (plane, wave), then their exclusive offsets
   __shared__ uint32_t s_sp;
+  __shared__ uint32_t s_lost;  // some outlier cell of this workgroup cannot carry its code
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   for (int i = tid; i < a.bklen; i += kSplThreads) s_hist[i] = 0;
+  if (tid == 0) s_lost = 0;
   const uint32_t X = a.X, Y = a.Y, Z = a.Z;
   const uint32_t ax = (X + 7) / 8, ay = (Y + 7) / 8;
   const int radius = a.radius;
@@ -284,6 +296,10 @@ __global__ void __launch_bounds__(kSplThreads, 4) k_spline3_c(SplineArgs<T> a)
         const size_t gid = gid0 + z * plane;
         const uint32_t pos = s_pc[z][wid] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
                                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        if ((uint32_t)cand + (1u << 24) > (1u << 25)) {  // |code| past 2^24: rare, and all that can be lost
+          const int half = (int)((uint32_t)cand - (uint32_t)radius);  // the stage's sum undone
+          if (half >= kSplCodeLim || half <= -kSplCodeLim || (T)(float)cand != (T)cand) s_lost = 1u;
+        }
         const uint64_t cell = make_cell((float)cand, (uint32_t)gid);
         if (pos < a.ol.cap_per_brick) slot[pos] = cell;
         else if (s_sp + (pos - a.ol.cap_per_brick) < a.ol.spill_cap) a.ol.spill[s_sp + (pos - a.ol.cap_per_brick)] = cell;
@@ -294,6 +310,7 @@ __global__ void __launch_bounds__(kSplThreads, 4) k_spline3_c(SplineArgs<T> a)
   __syncthreads();
   for (int i = tid; i < a.bklen; i += kSplThreads)
     if (s_hist[i]) atomicAdd(&a.hist[i], s_hist[i]);
+  if (tid == 0 && s_lost) *a.code_lost = 1u;
 }
 
 // ---- decompression ------------------------------------------------------------------------------

@@ -25,6 +25,19 @@ extern "C" {
 #define PSZ_AMD_ERR_DEVICE 102      /* a HIP runtime call, allocation or kernel launch failed       */
 #define PSZ_AMD_ERR_STATE 103       /* call out of order (compress_finish without a pending scan)   */
 #define PSZ_AMD_ERR_ENCODER 104     /* the encoder's own overflow / look-back check failed (a bug)  */
+#define PSZ_AMD_ERR_CODE_RANGE 105  /* spline: a quantisation code the archive cannot carry, below  */
+
+/* The spline predictor's domain.  A point whose code leaves [0, 2 radius) is stored as an outlier
+ * cell {f32 code, u32 index} (the reference's format), and the compressor predicts the following
+ * points from the exact code.  Compress (psz_compress_*, and psz_amd_compress_finish after a scan)
+ * returns PSZ_AMD_ERR_CODE_RANGE, and hands back no archive pointer, when
+ *   - double fields: some outlier's code is not a float, i.e. |prediction error| / (2 eb) beyond
+ *     2^24 (up to rounding: codes that a float holds exactly pass), or
+ *   - either dtype: |prediction error| / (2 eb) reaches 2^31 - 1024 (code + radius must stay an
+ *     int; an infinite value does so too, a NaN has no defined result with any predictor).
+ * float fields between 2^24 and that limit are accepted: both sides compute with the
+ * float-rounded code, and the error is one float ulp of the value.  Use a larger bound, or the
+ * Lorenzo predictor (its cells hold values, not codes). */
 
 /* Stage indices for psz_amd_stage_times (milliseconds of the last call, HIP events on the
  * manager's stream; only filled after psz_amd_enable_timing(m, 1)). */

@@ -48,10 +48,10 @@ def lib():
             f = getattr(L, name)
             f.restype = None
             f.argtypes = [_P, _P, _P, _SZ, _SZ, _SZ, _SZ, C.c_double, C.c_uint16, C.c_int, _P]
-        for name in ("orc_spline3_c_f32", "orc_spline3_c_f64"):
+        for name in ("orc_spline3_c_lost_f32", "orc_spline3_c_lost_f64"):
             f = getattr(L, name)
             f.restype = _SZ
-            f.argtypes = [_P, _SZ, _SZ, _SZ, C.c_double, C.c_int, _P, _P, _P, _P, _SZ]
+            f.argtypes = [_P, _SZ, _SZ, _SZ, C.c_double, C.c_int, _P, _P, _P, _P, _SZ, _P]
         for name in ("orc_spline3_x_f32", "orc_spline3_x_f64"):
             f = getattr(L, name)
             f.restype = None
@@ -134,9 +134,10 @@ def spline_anchor_len(dims):
     return ((x + 7) // 8) * ((y + 7) // 8) * ((z + 7) // 8)
 
 
-def spline3_c(data: np.ndarray, dims, eb: float, radius: int = 512):
+def spline3_c(data: np.ndarray, dims, eb: float, radius: int = 512, count_lost: bool = False):
     """cuSZ-i spline3 (parity unpinned) -> (codes u16[N], anchors T[A], ol_val f32[k], ol_idx u32[k]);
-    outliers in tile order, then (z,y,x) inside the 32x8x8 tile."""
+    outliers in tile order, then (z,y,x) inside the 32x8x8 tile.  count_lost: a fifth element, the
+    outliers whose code no cell carries (the library refuses such a field: PSZ_AMD_ERR_CODE_RANGE)."""
     data = np.ascontiguousarray(data)
     x, y, z = dims
     n = x * y * z
@@ -145,8 +146,11 @@ def spline3_c(data: np.ndarray, dims, eb: float, radius: int = 512):
     anchors = np.zeros(spline_anchor_len(dims), data.dtype)
     ov = np.zeros(max(n, 1), np.float32)
     oi = np.zeros(max(n, 1), np.uint32)
-    f = lib().orc_spline3_c_f64 if data.dtype == np.float64 else lib().orc_spline3_c_f32
-    k = f(_ptr(data), x, y, z, eb, radius, _ptr(codes), _ptr(anchors), _ptr(ov), _ptr(oi), n)
+    f = lib().orc_spline3_c_lost_f64 if data.dtype == np.float64 else lib().orc_spline3_c_lost_f32
+    lost = C.c_size_t(0)
+    k = f(_ptr(data), x, y, z, eb, radius, _ptr(codes), _ptr(anchors), _ptr(ov), _ptr(oi), n, C.byref(lost))
+    if count_lost:
+        return codes, anchors, ov[:k].copy(), oi[:k].copy(), int(lost.value)
     return codes, anchors, ov[:k].copy(), oi[:k].copy()
 
 

@@ -27,6 +27,10 @@
 #define SY 9
 #define SZ 9
 #define SIDX(x, y, z) ((x) + SX * ((y) + SY * (z)))
+/* the code domain (include/cusz_amd.h, PSZ_AMD_ERR_CODE_RANGE): |code / 2| < 2^31 - 1024 (exact in
+ * float), so that adding a radius of at most 512 stays an int; no code in the domain is -2^31 */
+#define CODE_LIM 2147482624.0
+#define CODE_LOST (-2147483648.0)
 
 typedef struct {
   unsigned bx, by, bz, gdx, gdy, gdz; /* tile index and grid (BIX.., GDX..) */
@@ -101,7 +105,9 @@ static int pred_ok(const tile_ctx* t, int inclusive, int x, int y, int z)
             const T err = s[i] - pred;                                                           \
             T code = FABS(err) * (T)eb_r + 1;                                                    \
             code = err < 0 ? -code : code;                                                       \
-            code = (T)((int)(code / 2) + radius);                                                \
+            /* past CODE_LIM the conversion is undefined in C (it saturates on the GPU) and      \
+             * code + radius leaves int: the point carries CODE_LOST, counted below */           \
+            code = FABS(code / 2) < (T)CODE_LIM ? (T)((int)(code / 2) + radius) : (T)CODE_LOST;  \
             e[i] = code;                                                                         \
             s[i] = pred + (code - radius) * (T)ebx2;                                             \
           } else {                                                                               \
@@ -136,15 +142,15 @@ static int pred_ok(const tile_ctx* t, int inclusive, int x, int y, int z)
     }                                                                                            \
   }                                                                                              \
                                                                                                  \
-  size_t orc_spline3_c_##SUF(const T* in, size_t X, size_t Y, size_t Z, double eb, int radius,   \
-                             uint16_t* codes, T* anchors, float* ol_val, uint32_t* ol_idx,       \
-                             size_t ol_cap)                                                      \
+  size_t orc_spline3_c_lost_##SUF(const T* in, size_t X, size_t Y, size_t Z, double eb, int radius,\
+                                  uint16_t* codes, T* anchors, float* ol_val, uint32_t* ol_idx,  \
+                                  size_t ol_cap, size_t* lost)                                   \
   {                                                                                              \
     const float eb_r = (float)(1.0 / eb), ebx2 = (float)(eb * 2.0); /* compressor.inl:107-108 */ \
     tile_ctx t = {0, 0, 0, (unsigned)((X + 31) / 32), (unsigned)((Y + 7) / 8), (unsigned)((Z + 7) / 8), X, Y, Z}; \
     const size_t ax = (X + 7) / 8, ay = (Y + 7) / 8;                                             \
     T s[SX * SY * SZ], e[SX * SY * SZ];                                                          \
-    size_t nol = 0;                                                                              \
+    size_t nol = 0, nlost = 0;                                                                   \
     for (t.bz = 0; t.bz < t.gdz; t.bz++)                                                         \
       for (t.by = 0; t.by < t.gdy; t.by++)                                                       \
         for (t.bx = 0; t.bx < t.gdx; t.bx++) {                                                   \
@@ -174,12 +180,23 @@ static int pred_ok(const tile_ctx* t, int inclusive, int x, int y, int z)
                 const int q = cand >= 0 && cand < 2 * radius;                                    \
                 codes[gid] = q ? (uint16_t)cand : 0;                                             \
                 if (!q) {                                                                        \
+                  /* a cell holds (float)code: lost when that is another number (f64 only:       \
+                   * in f32 cand is a float already) or the point left the domain above */       \
+                  if (cand == (T)CODE_LOST || (T)(float)cand != cand) nlost++;                   \
                   if (nol < ol_cap) ol_val[nol] = (float)cand, ol_idx[nol] = (uint32_t)gid;      \
                   nol++;                                                                         \
                 }                                                                                \
               }                                                                                  \
         }                                                                                        \
+    if (lost) *lost = nlost;                                                                     \
     return nol;                                                                                  \
+  }                                                                                              \
+                                                                                                 \
+  size_t orc_spline3_c_##SUF(const T* in, size_t X, size_t Y, size_t Z, double eb, int radius,   \
+                             uint16_t* codes, T* anchors, float* ol_val, uint32_t* ol_idx,       \
+                             size_t ol_cap)                                                      \
+  {                                                                                              \
+    return orc_spline3_c_lost_##SUF(in, X, Y, Z, eb, radius, codes, anchors, ol_val, ol_idx, ol_cap, NULL);\
   }                                                                                              \
                                                                                                  \
   void orc_spline3_x_##SUF(const uint16_t* codes, const T* anchors, const float* ol_val,         \

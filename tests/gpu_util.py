@@ -119,3 +119,63 @@ def check_phf_against_oracle(a, info, seg_o, layout):
     assert not np.any(a["bitstream"][gaps]), "nonzero cells between brick regions"
     assert a["total_nbit"] == int(info["par_nbit"].astype(np.int64).sum())
     assert a["total_ncell"] == a["bitstream"].size
+
+
+def spline_roundtrip(oracle, dims, dtype, eb, mode=cz.Abs, seed=5, data=None, radius=512, resource=None,
+                     decoders=(cz.DECODER_AUTO,), keep=None):
+    """One spline compress + decompress through the C-ABI against the CPU oracle, bit for bit: quant
+    codes, anchors, outlier cells (value bits, index AND order), histogram, Huffman segment and the
+    field decompressed into a NaN-poisoned buffer (by each of `decoders`).
+    data: the field (default: datagen.smooth3d_np(dims, seed)); resource: compress on this manager
+    and leave it open (default: a fresh one, closed at the end); keep: a dict that receives the
+    archive bytes.  -> (data, decompressed field, absolute eb, outlier count)."""
+    import torch
+
+    from cusz_amd import datagen
+
+    n = int(np.prod(dims))
+    if data is None:
+        data = datagen.smooth3d_np(dims, seed, dtype=dtype)
+    assert data.dtype == dtype and data.size == n
+    r = resource or cz.Resource(cz.F4 if dtype == np.float32 else cz.F8, dims, cz.Spline)
+    d_in = to_device(data)
+    ptr, nbytes, st = r.compress(d_in.data_ptr(), eb, mode, radius)
+    assert st == cz.PSZ_SUCCESS
+    arch = d2h(ptr, nbytes).tobytes()
+    if keep is not None:
+        keep["archive"] = arch
+    bklen = 2 * radius
+    a = parse_archive(arch, bklen)
+    h = a["header"]
+    assert h.entry[5] == nbytes and h.pipeline.predictor == cz.Spline
+    ebx = h.rc.eb  # absolute (Rel mode scaled by the range)
+    codes_o, anchors_o, ov_o, oi_o, lost = oracle.spline3_c(data, dims, ebx, radius, count_lost=True)
+    assert lost == 0, f"accepted a field with {lost} codes no cell carries"
+    ino = r.internals()
+    codes_g = d2h(ino.d_quant_codes, 2 * n, np.uint16)
+    bad = np.flatnonzero(codes_g != codes_o)
+    assert bad.size == 0, f"{bad.size} code mismatches, first {bad[:5]}"
+    anchors_g = np.frombuffer(arch[h.entry[1]:h.entry[2]], dtype)
+    np.testing.assert_array_equal(anchors_g.view(np.uint8), anchors_o.view(np.uint8))
+    np.testing.assert_array_equal(a["ol_idx"], oi_o)  # same deterministic order
+    np.testing.assert_array_equal(a["ol_val"].view(np.uint32), ov_o.view(np.uint32))
+    assert h.splen == len(oi_o)
+    np.testing.assert_array_equal(d2h(ino.d_hist, 4 * bklen, np.uint32), oracle.histogram(codes_o, bklen))
+    seg_o, _ = oracle.phf_segment(codes_o, bklen, sublen=a["sublen"],
+                                  books=expected_books(oracle, r, codes_o, dims, bklen, ino.layout, spline=True))
+    assert a["phf"] == seg_o
+    xo = oracle.spline3_x(codes_o, anchors_o, ov_o, oi_o, dims, ebx, radius)
+    ub = np.uint32 if dtype == np.float32 else np.uint64
+    for dec in decoders:
+        r.set_decoder(dec)
+        out = empty_device(n, torch.float32 if dtype == np.float32 else torch.float64)
+        out.fill_(float("nan"))
+        r.decompress(ptr, nbytes, out.data_ptr())
+        sync()
+        xg = out.cpu().numpy()
+        bad = np.flatnonzero(xg.view(ub) != xo.view(ub))
+        assert bad.size == 0, f"decoder {dec}: {bad.size} reconstruction mismatches, first {bad[:5]}"
+    r.set_decoder(cz.DECODER_AUTO)
+    if resource is None:
+        r.close()
+    return data, xg, ebx, len(oi_o)

@@ -10,7 +10,8 @@ import pytest
 
 import cusz_amd as cz
 from cusz_amd import datagen
-from gpu_util import d2h, empty_device, parse_archive, sync, to_device, expected_books
+from gpu_util import d2h, empty_device, parse_archive, sync, to_device
+from gpu_util import spline_roundtrip as _roundtrip
 
 pytestmark = pytest.mark.gpu
 
@@ -24,45 +25,6 @@ CASES = [
     ((33, 9, 9), np.float32, 3e-6),     # one tile plus its faces
     ((160, 96, 72), np.float64, 3e-6),
 ]
-
-
-def _roundtrip(oracle, dims, dtype, eb, mode=cz.Abs, seed=5):
-    import torch
-
-    n = int(np.prod(dims))
-    data = datagen.smooth3d_np(dims, seed, dtype=dtype)
-    r = cz.Resource(cz.F4 if dtype == np.float32 else cz.F8, dims, cz.Spline)
-    d_in = to_device(data)
-    ptr, nbytes, _ = r.compress(d_in.data_ptr(), eb, mode)
-    arch = d2h(ptr, nbytes).tobytes()
-    a = parse_archive(arch)
-    h = a["header"]
-    assert h.entry[5] == nbytes and h.pipeline.predictor == cz.Spline
-    ebx = h.rc.eb  # absolute (Rel mode scaled by the range)
-    codes_o, anchors_o, ov_o, oi_o = oracle.spline3_c(data, dims, ebx)
-    ino = r.internals()
-    codes_g = d2h(ino.d_quant_codes, 2 * n, np.uint16)
-    bad = np.flatnonzero(codes_g != codes_o)
-    assert bad.size == 0, f"{bad.size} code mismatches, first {bad[:5]}"
-    anchors_g = np.frombuffer(arch[h.entry[1]:h.entry[2]], dtype)
-    np.testing.assert_array_equal(anchors_g.view(np.uint8), anchors_o.view(np.uint8))
-    np.testing.assert_array_equal(a["ol_idx"], oi_o)  # same deterministic order
-    np.testing.assert_array_equal(a["ol_val"].view(np.uint32), ov_o.view(np.uint32))
-    np.testing.assert_array_equal(d2h(ino.d_hist, 4096, np.uint32), oracle.histogram(codes_o))
-    seg_o, _ = oracle.phf_segment(codes_o, 1024, sublen=a["sublen"],
-                                  books=expected_books(oracle, r, codes_o, dims, 1024, ino.layout, spline=True))
-    assert a["phf"] == seg_o
-    out = empty_device(n, torch.float32 if dtype == np.float32 else torch.float64)
-    out.fill_(float("nan"))
-    r.decompress(ptr, nbytes, out.data_ptr())
-    sync()
-    xg = out.cpu().numpy()
-    xo = oracle.spline3_x(codes_o, anchors_o, ov_o, oi_o, dims, ebx)
-    ub = np.uint32 if dtype == np.float32 else np.uint64
-    bad = np.flatnonzero(xg.view(ub) != xo.view(ub))
-    assert bad.size == 0, f"{bad.size} reconstruction mismatches, first {bad[:5]}"
-    r.close()
-    return data, xg, ebx, len(oi_o)
 
 
 @pytest.mark.parametrize("dims,dtype,eb", CASES)
