@@ -22,6 +22,7 @@ F4, F8 = 0, 1
 Abs, Rel = 0, 1
 Lorenzo, LorenzoZigZag, LorenzoProto, Spline = 0, 1, 2, 3
 Huffman, NullCodec = 0, 5
+FZCodec = 3  # the bit-plane shuffle + zero-word coder (include/cusz_amd.h, "The FZG codec")
 HistogramGeneric, HistogramSparse = 0, 1
 
 PSZ_SUCCESS = 0
@@ -236,14 +237,17 @@ class PszError(RuntimeError):
 class Resource:
     """Python mirror of psz_resource (cusz_rev1.h).  Pointers are device addresses."""
 
-    def __init__(self, dtype: int, dims, predictor: int = Lorenzo, stream: int = 0, header: psz_header = None):
+    def __init__(self, dtype: int, dims, predictor: int = Lorenzo, stream: int = 0, header: psz_header = None,
+                 codec: int = Huffman):
+        """codec: Huffman (default) or FZCodec (Lorenzo predictors only); a manager made from a
+        header takes the header's."""
         L = lib()
         if header is not None:
             self._h = L.psz_create_resource_manager_from_header(C.byref(header), C.c_void_p(stream))
         else:
             x, y, z = (tuple(dims) + (1, 1, 1))[:3]
             self._h = L.psz_create_resource_manager(
-                dtype, psz_len(x, y, z), psz_pipeline(predictor, HistogramGeneric, Huffman, NullCodec),
+                dtype, psz_len(x, y, z), psz_pipeline(predictor, HistogramGeneric, codec, NullCodec),
                 C.c_void_p(stream))
         if not self._h:
             raise PszError(L.psz_amd_last_create_status() or PSZ_AMD_ERR_DEVICE, "psz_create_resource_manager")

@@ -37,4 +37,24 @@ __device__ inline void write_headers_dev(uint8_t* archive, HeaderTpl t, unsigned
   for (int i = 64 / 4; i < 128 / 4; i++) p32[i] = 0;  // defined padding (reference: stale)
 }
 
+// one thread, an FZG archive (archive_layout.hh FzgLayout): the psz header and the 32-B segment
+// header, whose template lies in t.phf[0..8).  nc: the payload in 4-byte cells (two a word), so that
+// the outlier cells follow at payload_rel + 4 nc as they follow a bitstream of nc cells.
+__device__ inline void write_headers_fzg_dev(uint8_t* archive, HeaderTpl t, unsigned long long nc, unsigned long long sp,
+                                             size_t fzg_offset, size_t payload_rel)
+{
+  const unsigned long long words = nc / 2;
+  t.phf[6] = (uint32_t)words, t.phf[7] = (uint32_t)(words >> 32);
+  uint32_t* psz = t.psz;
+  const uint32_t e_spfmt = (uint32_t)(fzg_offset + payload_rel + nc * 4);
+  psz[14 + 3] = e_spfmt;
+  psz[14 + 4] = (uint32_t)(e_spfmt + sp * 8);
+  psz[14 + 5] = (uint32_t)(e_spfmt + sp * 8);
+  psz[26] = (uint32_t)sp, psz[27] = (uint32_t)(sp >> 32);
+  uint32_t* a32 = reinterpret_cast<uint32_t*>(archive);
+  for (int i = 0; i < 176 / 4; i++) a32[i] = psz[i];
+  uint32_t* f32 = reinterpret_cast<uint32_t*>(archive + fzg_offset);
+  for (int i = 0; i < 32 / 4; i++) f32[i] = t.phf[i];
+}
+
 }  // namespace cusz_amd

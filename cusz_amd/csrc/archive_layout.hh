@@ -2,7 +2,8 @@
 // the one host-side definition every writer (pipeline.cc's compress paths, merge.cc) and reader
 // (the decode launches) takes its offsets from.  Host only, no HIP header: g++ alone compiles it
 // (tests/host/layout_shim.cc).  archive_device.hh fills the size-dependent header fields on the
-// device and relies on the same layout.
+// device and relies on the same layout.  The FZG segment (codec1 = FZCodec), which takes the phf
+// segment's place, is defined the same way at the end: FzgLayout to write, FzgView to read and check.
 //
 //   archive = [psz_header 176][anchors (spline)][phf segment][outlier cells]     (cusz/header.h)
 //   phf     = [phf_header, padded to 128][revbook][par_nbit u32[pardeg]][par_entry u32[pardeg]]
@@ -86,6 +87,75 @@ struct PhfView {
     bits_rel = l.bits_rel;
     const size_t bits_off = phf_off + l.bits_rel, total = h->entry[PSZHEADER_ENC_PASS2_END];
     bs_words = total > bits_off ? (total - bits_off) / 4 : 0;
+  }
+};
+
+// ---- the FZG segment (codec1 = FZCodec; DESIGN.md §4, "The FZG codec") -----------------------
+//   fzg = [FzgHeader 32][flags u64[units]][block_off u32[blocks + 1], padded to 8][payload u64[total_words]]
+// It takes the phf segment's place at entry[PSZHEADER_ENCODED]; the outlier cells follow it.  A
+// unit is 256 symbols (one wave64, 64 bit-plane words, flag bit w = word w is nonzero), a block is
+// 16 units; block_off[b] counts the payload words before block b.
+constexpr uint32_t kFzgMagic = 0x31475A46u;  // "FZG1"
+constexpr uint32_t kFzgUnit = 256, kFzgBlockUnits = 16, kFzgBlock = kFzgUnit * kFzgBlockUnits;
+enum : uint32_t { kFzgPlain = 0, kFzgZigzagDelta = 1 };  // symbol = code | zigzag(code - radius)
+
+struct FzgHeader {
+  uint32_t magic, unit, transform, units, blocks, reserved;
+  uint64_t total_words;  // filled on the device
+};
+static_assert(sizeof(FzgHeader) == 32 && offsetof(FzgHeader, total_words) == 24, "FZG header");
+
+struct FzgLayout {
+  static constexpr size_t fzg_off = sizeof(psz_header);  // Lorenzo only: no anchors
+  size_t units, blocks;
+  static constexpr size_t flags_rel = sizeof(FzgHeader);
+  size_t off_rel, payload_rel;  // sections, from the segment's start
+  explicit FzgLayout(size_t n)
+      : units((n + kFzgUnit - 1) / kFzgUnit),
+        blocks((n + kFzgBlock - 1) / kFzgBlock),
+        off_rel(flags_rel + 8 * units),
+        payload_rel((off_rel + 4 * (blocks + 1) + 7) & ~(size_t)7)
+  {
+  }
+  // every bit-plane word nonzero: 64 words a unit
+  size_t worst_bytes() const { return payload_rel + 512 * units; }
+};
+
+// the psz header's static fields of an FZG archive and the segment header's (total_words: device)
+inline void fill_fzg_templates(const FzgLayout& l, uint32_t transform, psz_len len, psz_header* h, FzgHeader* fh)
+{
+  h->vle_sublen = (int)kFzgBlock;
+  h->vle_pardeg = (int)l.blocks;
+  h->len = len;
+  h->entry[PSZHEADER_HEADER] = 0;
+  h->entry[PSZHEADER_ANCHOR] = (uint32_t)sizeof(psz_header);
+  h->entry[PSZHEADER_ENCODED] = (uint32_t)l.fzg_off;
+  *fh = FzgHeader{kFzgMagic, kFzgUnit, transform, (uint32_t)l.units, (uint32_t)l.blocks, 0u, 0ull};
+}
+
+// The decode side.  Before any launch the host checks the psz header's entries, the segment's own
+// header and its last offset word (`fh` and `last_off`: the caller's copies of the segment's first
+// 32 bytes and of block_off[blocks]; read them only after span_ok()).  ok() false: a bad archive.
+struct FzgView {
+  FzgLayout l;
+  size_t seg_off, seg_bytes;  // the segment inside the archive (entry[ENCODED] .. entry[SPFMT])
+  bool entries_ok;
+
+  FzgView(const psz_header* h, size_t n) : l(n)
+  {
+    const uint32_t* e = h->entry;
+    seg_off = e[PSZHEADER_ENCODED];
+    entries_ok = e[PSZHEADER_SPFMT] >= e[PSZHEADER_ENCODED] && e[PSZHEADER_ENC_PASS2_END] >= e[PSZHEADER_SPFMT];
+    seg_bytes = entries_ok ? e[PSZHEADER_SPFMT] - e[PSZHEADER_ENCODED] : 0;
+  }
+  // the header, flags and offsets lie inside the segment, 8-byte aligned in the archive
+  bool span_ok() const { return entries_ok && seg_off % 8 == 0 && seg_off >= sizeof(psz_header) && seg_bytes >= l.payload_rel; }
+  size_t last_off_rel() const { return l.off_rel + 4 * l.blocks; }
+  bool ok(const FzgHeader& fh, uint32_t last_off) const
+  {
+    return span_ok() && fh.magic == kFzgMagic && fh.unit == kFzgUnit && fh.transform <= kFzgZigzagDelta &&
+           fh.units == l.units && fh.blocks == l.blocks && fh.total_words == last_off &&
+           fh.total_words <= 64 * l.units && seg_bytes == l.payload_rel + 8 * fh.total_words;
   }
 };
 

@@ -55,6 +55,7 @@ static void usage()
 {
   std::printf(
       "usage: cusz -z -t f32|f64 -m abs|rel|r2r -e EB -l X[xY[xZ]] -i FILE [-p lrz|lrz-zz] [-R time,cr]\n"
+      "               [--codec huffman|fzgcodec]  (fzgcodec: no codebook, lrz / lrz-zz only; -x reads it from the archive)\n"
       "       cusz -x -i FILE.cusza [--origin FILE] [-R time] [-S write2disk]\n"
       "               [--region X0[,Y0[,Z0]]:EX[,EY[,EZ]]]  (decode only this box, in elements)\n");
 }

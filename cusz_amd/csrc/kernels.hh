@@ -104,6 +104,32 @@ struct HfDecodeArgs {  // its first five fields: a PhfView's (archive_layout.hh)
 };
 int launch_hf_decode(const HfDecodeArgs& a, hipStream_t st);
 
+// ---- FZG codec (fzg.hip): bit-plane shuffle + zero-word coder, archive_layout.hh FzgLayout ----
+// symbols: the codes (transform kFzgPlain) or zigzag(code - radius) (kFzgZigzagDelta)
+struct FzgEncodeArgs {
+  const uint16_t* codes;  // index order, 8-byte aligned
+  size_t n;
+  int radius;
+  uint32_t transform;
+  uint64_t* flags;        // segment sections (8-byte aligned)
+  uint32_t* block_off;
+  uint64_t* payload;
+  CompressInfo* info;     // total_ncell <- the payload in 4-byte cells (two a word)
+};
+// sizing (flags, words per block) -> one-workgroup scan (block_off, total) -> packing
+int launch_fzg_encode(const FzgEncodeArgs& a, hipStream_t st);
+struct FzgDecodeArgs {
+  const uint64_t* flags;
+  const uint32_t* block_off;
+  const uint64_t* payload;
+  uint64_t total_words;   // loads at or past it read 0 (a corrupt flag or offset stays inside the archive)
+  size_t n;
+  int radius;
+  uint32_t transform;
+  uint16_t* codes;        // 8-byte aligned
+};
+int launch_fzg_decode(const FzgDecodeArgs& a, hipStream_t st);
+
 // ---- pipeline glue (pipeline_kernels.hip) ---------------------------------------------------
 struct FinalizeArgs {
   // Huffman
@@ -122,10 +148,12 @@ struct FinalizeArgs {
   bool sizes_known = false;  // brick path: total_nbit / total_ncell already in info (reservation)
   bool nbit_known = false;   // info->total_nbit already summed (the encoder's tile-sum pass)
 };
-// psz_tpl / phf_tpl non-null: the same workgroup also writes both headers (no separate launch)
+// psz_tpl / phf_tpl non-null: the same workgroup also writes both headers (no separate launch).
+// fzg: phf_tpl is an FzgHeader, phf_offset / bitstream_rel its segment's offset and its payload's,
+// and info->total_ncell the payload in 4-byte cells (sizes_known)
 int launch_finalize_scan(const FinalizeArgs& a, hipStream_t st, const void* psz_tpl = nullptr,
                          const void* phf_tpl = nullptr, uint8_t* archive = nullptr, size_t phf_offset = 0,
-                         size_t bitstream_rel = 0);
+                         size_t bitstream_rel = 0, bool fzg = false);
 
 struct OutlierCopyArgs {
   const uint64_t* slots;

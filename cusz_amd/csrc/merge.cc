@@ -90,6 +90,8 @@ extern "C" int psz_amd_merge_archives(const uint8_t* const* parts, const size_t*
     if (part_bytes[i] < sizeof(psz_header)) return PSZ_AMD_ERR_BAD_ARCHIVE;
     std::memcpy(&p.h, parts[i], sizeof(psz_header));
     const uint32_t* e = p.h.entry;
+    // FZG parts (block offsets to rebase, flags to concatenate) are not merged here
+    if (p.h.pipeline.codec1 != Huffman) return PSZ_ABORT_NO_SUCH_CODEC;
     // anchors (spline) are per-slab 8^3 lattices: not mergeable by concatenation
     if (e[PSZHEADER_ANCHOR] != e[PSZHEADER_ENCODED]) return PSZ_ABORT_NO_SUCH_PREDICTOR;
     if (e[PSZHEADER_ENC_PASS2_END] > part_bytes[i] || e[PSZHEADER_ENCODED] + sizeof(phf_header) > part_bytes[i])

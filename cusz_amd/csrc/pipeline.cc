@@ -10,6 +10,8 @@
 //              -> finalize: outlier compaction + headers written on device
 //              -> one 176-B header read-back (compress is synchronous, as in the reference)
 //   decompress: outlier scatter -> Huffman decode -> Lorenzo reconstruct (queued, no sync)
+//   codec1 = FZCodec (Lorenzo only): predict -> FZG encode (fzg.hip: no codebook stage) -> finalize;
+//              decompress: segment check (one 36-B read-back) -> scatter -> FZG decode -> reconstruct
 //
 // The reference does 5+ host round trips per compress and copies a 2N-byte buffer
 // (SURVEY.md §3.1); here the archive is assembled in place.
@@ -71,7 +73,8 @@ static int region_plan(const psz_header* h, psz_len o, psz_len e, psz_amd_region
   const int nd = ndim_of(l);
   const BrickGeom g = brick_geom(nd, l.x, l.y, l.z, h->dtype == F8 ? 8 : 4);
   // (the decoder finds a brick row's chunk by its position: one chunk per row of 256)
-  const bool fused = g.ok && nd == 3 && h->pipeline.predictor == Lorenzo && h->vle_sublen == g.W &&
+  // (an FZG archive has no Huffman chunks to pick bricks by: the whole field, then the box)
+  const bool fused = g.ok && nd == 3 && h->pipeline.predictor == Lorenzo && h->pipeline.codec1 == Huffman && h->vle_sublen == g.W &&
                      h->vle_pardeg > 0 && (uint32_t)h->vle_pardeg == g.nchunks && 2 * (int)h->rc.radius <= kMaxBklen;
   if (fused) {
     const RegionBox b = region_box((uint32_t)o.x, (uint32_t)o.y, (uint32_t)o.z, (uint32_t)e.x, (uint32_t)e.y,
@@ -436,6 +439,10 @@ struct Pipeline {
     const size_t chunks = std::max((size_t)pardeg, bl.g.ok ? (size_t)bl.g.nchunks : 0);
     const PhfLayout lay((size_t)elem_bytes * sgeom.anchor_len, kMaxBklen, chunks);
     archive_cap = lay.phf_off + lay.bits_rel + 4 * (bitstream_cells_cap() + chunks) + 8 * (ol_cells + spill_cap) + 64;
+    // an FZG archive's worst case (every bit-plane word nonzero: 2 n bytes of payload + flags +
+    // offsets) lies below the Huffman bound of 27 bits a symbol; sized explicitly all the same
+    const FzgLayout fz(n);
+    archive_cap = std::max(archive_cap, fz.fzg_off + fz.worst_bytes() + 8 * (ol_cells + spill_cap) + 64);
     return d_archive.alloc(archive_cap);
   }
 
@@ -499,6 +506,7 @@ struct Pipeline {
   // state carried from compress_scan (pass 1) to compress_finish (codebook onwards)
   struct Pending {
     bool active = false, brick = false, spl = false, zz = false;
+    bool fzg = false;         // codec1 = FZCodec: finish with the FZG encode (no codebook)
     int radius = 0;
     uint32_t hist_epoch = 0;  // != 0: the scan published d_hist to h_hist() with this epoch (flag 2)
     bool ext = false;         // finish with a caller's (reduced) histogram + overflow word
@@ -574,7 +582,8 @@ struct Pipeline {
     for (int run = 0;; run++) {
       const int g0 = grow_events;
       int s;
-      if (codebook == PSZ_AMD_CODEBOOK_STREAM && bl.g.ndim == 3 && use_brick(h->pipeline.predictor))
+      if (codebook == PSZ_AMD_CODEBOOK_STREAM && bl.g.ndim == 3 && use_brick(h->pipeline.predictor) &&
+          h->pipeline.codec1 != FZCodec)  // (the codebook knob does not apply to FZG)
         s = compress_sampled<T>(h, in, out, outlen);
       else {
         s = compress_scan<T>(h, in, true);
@@ -600,7 +609,9 @@ struct Pipeline {
     pend.side_book = false;
     const psz_predictor pred = h->pipeline.predictor;
     if (pred != Lorenzo && pred != LorenzoZigZag && pred != Spline) return PSZ_ABORT_NO_SUCH_PREDICTOR;
-    if (h->pipeline.codec1 != Huffman) return PSZ_ABORT_NO_SUCH_CODEC;
+    // FZG (fzg.hip): Lorenzo's codes in index order, whatever the layout and codebook knobs say
+    const bool fzg = h->pipeline.codec1 == FZCodec;
+    if ((h->pipeline.codec1 != Huffman && !fzg) || (fzg && pred == Spline)) return PSZ_ABORT_NO_SUCH_CODEC;
     const bool zz = pred == LorenzoZigZag;
     const bool spl = pred == Spline;
     if (spl && !d_spl_slots) {  // spline outlier slots: one range per 32x8x8 tile, allocated on first use
@@ -614,7 +625,7 @@ struct Pipeline {
     const int bklen = 2 * radius;
     if (radius < 1 || bklen > kMaxBklen) return PSZ_AMD_ERR_INVALID_ARG;
 
-    const bool brick = use_brick(pred);
+    const bool brick = !fzg && use_brick(pred);
     // chunk length: the caller's, else the tuned one
     if (!brick) {
       const int s = user_sublen ? std::min(8192, ((user_sublen + 255) / 256) * 256) : tuned_sublen;
@@ -637,7 +648,7 @@ struct Pipeline {
         regions({{d_hist, nullptr, (size_t)(bklen + 1) * 4}, {d_small, nullptr, kSmallZeroBytes}, {z3, nullptr, z3_bytes}}), stream));
     mark(1);
     last_layout = brick ? PSZ_AMD_LAYOUT_BRICK : PSZ_AMD_LAYOUT_REFERENCE;
-    pend.brick = brick, pend.spl = spl, pend.radius = radius, pend.zz = zz;
+    pend.brick = brick, pend.spl = spl, pend.radius = radius, pend.zz = zz, pend.fzg = fzg;
     pend.anchor_bytes = spl ? sizeof(T) * sgeom.anchor_len : 0;
     if (brick) {
       OutlierSink bol{d_slots, d_brick_cnt, d_spill, spill_cnt(), brick_cap(), spill_cap, nullptr};
@@ -693,7 +704,7 @@ struct Pipeline {
       // the kernel's last workgroup publishes the histogram to the host (no publish launch) for
       // the host's reference codebook (every mode: measured faster than the device book here)
       HostPub hp;
-      if (pub_hist)
+      if (pub_hist && !fzg)  // (FZG builds no book)
         hp = HostPub{regions({{h_hist(), d_hist, (size_t)bklen * 4}}), const_cast<uint32_t*>(flag(2)), ++epoch,
                      hist_ticket()};
       pend.hist_epoch = hp.epoch;
@@ -719,6 +730,7 @@ struct Pipeline {
       pend.hist_epoch = 0;  // the scan's published histogram is not the one to encode with
     }
     if (pend.brick) return compress_brick(h, out, outlen, radius);
+    if (pend.fzg) return compress_fzg(h, out, outlen);
     const bool spl = pend.spl;
     const size_t anchor_bytes = pend.anchor_bytes;
     uint64_t* slots = spl ? d_spl_slots : d_slots;
@@ -779,6 +791,41 @@ struct Pipeline {
     mark(5);
     if (book.armed)
       if (int fs = book.build(false)) return fs;
+    return finish_compress(h, out, outlen);
+  }
+
+  // FZG finish: no codebook stage (the histogram is produced for psz_amd_compress_scan_*'s export
+  // and not used; of a caller's histogram only the overflow word counts) -> FZG encode into the
+  // archive -> finalize as on the Huffman path, the payload's 4-byte cells in the bitstream's role.
+  int compress_fzg(psz_header* h, uint8_t** out, size_t* outlen)
+  {
+    mark(3);
+    const FzgLayout lay(n);
+    uint8_t* seg = d_archive + lay.fzg_off;
+    const uint32_t transform = pend.zz ? kFzgPlain : kFzgZigzagDelta;
+    const FzgEncodeArgs ea{d_codes,
+                           n,
+                           pend.radius,
+                           transform,
+                           reinterpret_cast<uint64_t*>(seg + lay.flags_rel),
+                           reinterpret_cast<uint32_t*>(seg + lay.off_rel),
+                           reinterpret_cast<uint64_t*>(seg + lay.payload_rel),
+                           info()};
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_fzg_encode(ea, stream));
+    mark(4);
+    FzgHeader fh;
+    fill_fzg_templates(lay, transform, len, h, &fh);
+    FinalizeArgs fa{nullptr, nullptr, 0, d_brick_cnt, geom.nbricks, cap_per_brick, spill_cnt(), spill_cap, d_brick_off, info()};
+    fa.sizes_known = true;  // info()->total_ncell: the encode's scan
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_finalize_scan(fa, stream, h, &fh, d_archive, lay.fzg_off, lay.payload_rel, true));
+    OutlierCopyArgs oa{d_slots, d_brick_cnt, d_brick_off, geom.nbricks, cap_per_brick, d_spill, spill_cnt(), spill_cap,
+                       info(), d_archive, lay.fzg_off + lay.payload_rel};
+    const HostPub sp{readback_regions(), const_cast<uint32_t*>(flag(3)), ++epoch, summary_ticket()};
+    const bool in_copy = geom.nbricks <= 4096u;  // as compress_finish
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_outlier_copy(oa, stream, in_copy ? sp : HostPub{}));
+    if (!in_copy) CUSZ_AMD_HIP_CHECK((hipError_t)launch_publish(sp.r, sp.flag, sp.epoch, stream));
+    summary_epoch = sp.epoch;
+    mark(5);
     return finish_compress(h, out, outlen);
   }
 
@@ -848,7 +895,7 @@ struct Pipeline {
   {
     pend.active = false;
     pend.ext = false;  // no caller's overflow word in this mode (finish_compress reads it when set)
-    pend.spl = false, pend.brick = true;
+    pend.spl = false, pend.brick = true, pend.fzg = false;
     if (h->pipeline.codec1 != Huffman) return PSZ_ABORT_NO_SUCH_CODEC;
     const bool zz = h->pipeline.predictor == LorenzoZigZag;
     const int radius = h->rc.radius, bklen = 2 * radius;
@@ -960,7 +1007,7 @@ struct Pipeline {
     if (timing) {
       stage_ms[PSZ_AMD_T_EXTREMA] = span(0, 1);
       stage_ms[PSZ_AMD_T_PREDICT] = span(1, 2);
-      stage_ms[PSZ_AMD_T_BOOK] = span(2, 3);
+      stage_ms[PSZ_AMD_T_BOOK] = pend.fzg ? 0.f : span(2, 3);  // FZG: no codebook stage
       stage_ms[PSZ_AMD_T_ENCODE] = span(3, 4);
       stage_ms[PSZ_AMD_T_FINALIZE] = span(4, 5);
       stage_ms[PSZ_AMD_T_COMPRESS] = span(0, 5);
@@ -998,10 +1045,50 @@ struct Pipeline {
     return PSZ_SUCCESS;
   }
 
+  // An FZG archive before any launch: the psz header's entries on the host, then the segment's own
+  // 32-byte header and its last offset word, read back in one small synchronous copy (the only
+  // host wait of an FZG decode).  Everything the decode kernel then loads lies inside the segment;
+  // flags and offsets inside it that are corrupt are clamped on the device.
+  int check_fzg(const psz_header* h, const uint8_t* in, FzgHeader* fh)
+  {
+    const psz_predictor pred = h->pipeline.predictor;
+    if (pred != Lorenzo && pred != LorenzoZigZag) return PSZ_ABORT_NO_SUCH_CODEC;
+    if (h->len.x * h->len.y * h->len.z != n) return PSZ_ABORT_UNSUPPORTED_DIMENSION;
+    if (reinterpret_cast<uintptr_t>(in) % 8) return PSZ_AMD_ERR_INVALID_ARG;  // u64 flags and words
+    const FzgView v(h, n);
+    if (!v.span_ok()) return PSZ_AMD_ERR_BAD_ARCHIVE;
+    uint32_t last_off = 0;
+    CUSZ_AMD_HIP_CHECK(hipMemcpyAsync(fh, in + v.seg_off, sizeof(FzgHeader), hipMemcpyDeviceToHost, stream));
+    CUSZ_AMD_HIP_CHECK(hipMemcpyAsync(&last_off, in + v.seg_off + v.last_off_rel(), 4, hipMemcpyDeviceToHost, stream));
+    CUSZ_AMD_HIP_CHECK(hipStreamSynchronize(stream));
+    return v.ok(*fh, last_off) ? PSZ_SUCCESS : PSZ_AMD_ERR_BAD_ARCHIVE;
+  }
+
+  int decode_fzg(const psz_header* h, const uint8_t* in, const FzgHeader& fh)
+  {
+    const FzgView v(h, n);
+    const uint8_t* seg = in + v.seg_off;
+    const FzgDecodeArgs da{reinterpret_cast<const uint64_t*>(seg + v.l.flags_rel),
+                           reinterpret_cast<const uint32_t*>(seg + v.l.off_rel),
+                           reinterpret_cast<const uint64_t*>(seg + v.l.payload_rel),
+                           fh.total_words,
+                           n,
+                           (int)h->rc.radius,
+                           fh.transform,
+                           d_codes};
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_fzg_decode(da, stream));
+    return PSZ_SUCCESS;
+  }
+
   int decode_codes(const psz_header* h, const uint8_t* in)
   {
     // the decoders write d_codes, which a pending compress_finish would pack (as decompress)
     pend.active = false;
+    if (h->pipeline.codec1 == FZCodec) {  // (the decoder knob does not apply)
+      FzgHeader fh;
+      if (const int s = check_fzg(h, in, &fh)) return s;
+      return decode_fzg(h, in, fh);
+    }
     const PhfView v(h, in);
     const int pd = v.pardeg, sl = v.sublen;
     if (sl % 64 == 0 && sl <= 8192 && decoder == 0 && pd > 0 && v.bklen <= kMaxBklen) {  // the fused decoders' chunk loop
@@ -1027,10 +1114,16 @@ struct Pipeline {
     if (pred != Lorenzo && pred != LorenzoZigZag && pred != Spline) return PSZ_ABORT_NO_SUCH_PREDICTOR;
     const bool zz = pred == LorenzoZigZag;
     if (h->len.x != len.x || h->len.y != len.y || h->len.z != len.z) return PSZ_ABORT_UNSUPPORTED_DIMENSION;
+    // an FZG archive is checked before anything is written (`out` stays as it is on a bad one)
+    const bool fzg = h->pipeline.codec1 == FZCodec;
+    FzgHeader fh{};
+    if (fzg)
+      if (const int s = check_fzg(h, in, &fh)) return s;
     if (pred == Spline) return decompress_spline<T>(h, in, out);
     mark(6);
-    // fused decode + reconstruct: 3-D and 1-D (2-D linear-brick archives decode chunk by chunk)
-    const bool brickdec = bl.g.ok && bl.g.ndim != 2 && decoder == 0 && h->vle_sublen == bl.g.W &&
+    // fused decode + reconstruct: 3-D and 1-D (2-D linear-brick archives decode chunk by chunk);
+    // never an FZG archive, whatever its vle_sublen says
+    const bool brickdec = !fzg && bl.g.ok && bl.g.ndim != 2 && decoder == 0 && h->vle_sublen == bl.g.W &&
                           2 * h->rc.radius <= kMaxBklen;
     const uint32_t* cells = reinterpret_cast<const uint32_t*>(in + h->entry[PSZHEADER_SPFMT]);
     X1dOutliers ox;  // 1-D: the reconstruction reads sorted cells directly (no scatter pass)
@@ -1060,7 +1153,7 @@ struct Pipeline {
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_scatter<T>(cells, h->splen, out, n, stream, ox.unsorted, ox.epoch));
     mark(7);
     if (brickdec) return decompress_brick<T>(h, in, out, zz, bo);
-    int s = decode_codes(h, in);
+    int s = fzg ? decode_fzg(h, in, fh) : decode_codes(h, in);
     if (s) return s;
     mark(8);
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_lorenzo_x<T>(d_codes, out, len.x, len.y, len.z, h->rc.eb, h->rc.radius,

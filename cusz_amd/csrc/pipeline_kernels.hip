@@ -114,7 +114,9 @@ __global__ void __launch_bounds__(1024) k_finalize_scan(FinalizeArgs a, HeaderTp
     a.info->splen = (unsigned long long)slot_total + (a.spill_start ? 0u : sp_kept);
     a.info->outlier_lost = sp > a.spill_cap ? sp - a.spill_cap : 0u;
     a.info->spilled = sp;
-    if (write_hdr)
+    if (write_hdr == 2)  // an FZG archive: phf_offset / bitstream_rel are its segment's and its payload's
+      write_headers_fzg_dev(archive, hdr, ncell, a.info->splen, phf_offset, bitstream_rel);
+    else if (write_hdr)
       write_headers_dev(archive, hdr, a.info->total_nbit, ncell, a.info->splen, phf_offset, bitstream_rel);
   }
 }
@@ -372,16 +374,17 @@ int launch_upload(const XferRegions& r, hipStream_t st)
 }
 
 int launch_finalize_scan(const FinalizeArgs& a, hipStream_t st, const void* psz_tpl, const void* phf_tpl,
-                         uint8_t* archive, size_t phf_offset, size_t bitstream_rel)
+                         uint8_t* archive, size_t phf_offset, size_t bitstream_rel, bool fzg)
 {
   int grid = (a.pardeg + 255) / 256;
   grid = grid < 1 ? 1 : (grid > 128 ? 128 : grid);
   if (!a.sizes_known && !a.nbit_known) k_sum_nbit<<<grid, 256, 0, st>>>(a.par_nbit, a.pardeg, &a.info->total_nbit);
   HeaderTpl t;
-  const int wh = psz_tpl && phf_tpl && archive;
+  const int wh = psz_tpl && phf_tpl && archive ? (fzg ? 2 : 1) : 0;
   if (wh) {
+    __builtin_memset(&t, 0, sizeof(t));
     __builtin_memcpy(t.psz, psz_tpl, 176);
-    __builtin_memcpy(t.phf, phf_tpl, 64);
+    __builtin_memcpy(t.phf, phf_tpl, fzg ? sizeof(FzgHeader) : 64);
   }
   else
     __builtin_memset(&t, 0, sizeof(t));

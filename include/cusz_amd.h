@@ -44,12 +44,12 @@ extern "C" {
 enum {
   PSZ_AMD_T_EXTREMA = 0,   /* Rel mode range probe                         */
   PSZ_AMD_T_PREDICT = 1,   /* Lorenzo predict-quantize + histogram + outliers */
-  PSZ_AMD_T_BOOK = 2,      /* histogram D2H + host codebook + H2D          */
-  PSZ_AMD_T_ENCODE = 3,    /* Huffman encode (bit packing + look-back)      */
+  PSZ_AMD_T_BOOK = 2,      /* histogram D2H + host codebook + H2D (FZG: 0)  */
+  PSZ_AMD_T_ENCODE = 3,    /* Huffman encode (bit packing + look-back); FZG: its three launches */
   PSZ_AMD_T_FINALIZE = 4,  /* outlier compaction + headers + readback       */
   PSZ_AMD_T_COMPRESS = 5,  /* whole compress call                           */
   PSZ_AMD_T_SCATTER = 6,   /* decompress: outlier scatter (+ zeroing)       */
-  PSZ_AMD_T_DECODE = 7,    /* decompress: Huffman decode                    */
+  PSZ_AMD_T_DECODE = 7,    /* decompress: Huffman decode; FZG: its decode launch */
   PSZ_AMD_T_RECON = 8,     /* decompress: Lorenzo reconstruct               */
   PSZ_AMD_T_DECOMPRESS = 9,/* whole decompress call                         */
   PSZ_AMD_T_COUNT = 10
@@ -125,6 +125,47 @@ int psz_amd_set_layout(psz_resource* m, int layout);
 #define PSZ_AMD_CODEBOOK_SAMPLED 1
 #define PSZ_AMD_CODEBOOK_STREAM 2
 int psz_amd_set_codebook(psz_resource* m, int mode);
+
+/* ---- the FZG codec: psz_pipeline.codec1 = FZCodec (cusz/type.h; `cusz --codec fzgcodec`) ----
+ * A second lossless stage for callers who prefer throughput to ratio: no histogram, no codebook, no
+ * host round trip, nothing data-dependent serial.  Lorenzo and LorenzoZigZag, 1-D to 3-D, f32 and
+ * f64; Spline with FZCodec returns PSZ_ABORT_NO_SUCH_CODEC, as every codec but Huffman and FZCodec
+ * does.  The quant codes, the outlier cells, the error bound and the decompressed field are those
+ * of the Huffman path; only the segment at entry[PSZHEADER_ENCODED] differs.  The reference ships a
+ * codec of this family without wiring it into its pipeline, so there is no reference format to
+ * match: this one is this build's own, and the archive is a pure function of the codes.
+ *
+ * Format.  Symbols are the u16 codes in index order, as they are (LorenzoZigZag, transform 0) or
+ * as zigzag(code - radius) (Lorenzo, transform 1: small deltas of either sign keep only low bits,
+ * the outlier code 0 becomes 2 radius - 1).  A unit is 256 consecutive symbols: lane l of 64 holds
+ * symbols 4l..4l+3 as one little-endian u64, and word w (0..63) of the unit has bit l = bit w of
+ * lane l's u64 (a 64 x 64 bit transpose).  The unit's flag has bit w set iff word w is nonzero; its
+ * payload is its nonzero words in ascending w.  Symbols past the field's end count as 0.
+ *   segment = u32 magic "FZG1" | u32 unit = 256 | u32 transform | u32 units | u32 blocks | u32 0
+ *             | u64 payload words                                                 (32 bytes)
+ *           | u64 flags[units]
+ *           | u32 block_off[blocks + 1]: payload words before each block of 16 units (4096
+ *             symbols), [blocks] = the total; padded to 8 bytes
+ *           | u64 payload[words], unit after unit, no gaps
+ * psz_header: pipeline.codec1 = FZCodec, vle_sublen = 4096, vle_pardeg = blocks, entry[] and splen
+ * as for Huffman; the outlier cells follow the segment.  Worst case: 2 bytes a symbol + 1/32 +
+ * 1/1024; the manager's archive capacity covers it.
+ *
+ * Decompression reads the codec from the header.  Before anything is queued the segment is
+ * checked (the header's entries on the host; the segment's 32-byte header and last offset in one
+ * small synchronous read-back, the only host wait): magic, unit size, unit and block counts
+ * against the field, the segment inside the archive, offsets and payload inside the segment.  A
+ * violation returns PSZ_AMD_ERR_BAD_ARCHIVE with nothing launched and nothing written.  Corrupt
+ * flags or offsets inside a well-formed segment give wrong values, never a read outside it.  The
+ * archive pointer must be 8-byte aligned (PSZ_AMD_ERR_INVALID_ARG otherwise).
+ *
+ * What does not apply: psz_amd_set_sublen / _decoder / _layout / _codebook are accepted and have
+ * no effect on an FZG compress or decompress (the codes always take the reference layout;
+ * psz_amd_internals.layout says so).  psz_amd_compress_scan_* still exports the histogram; of the
+ * histogram passed to psz_amd_compress_finish only the overflow word counts.  Stage times:
+ * PSZ_AMD_T_BOOK is 0, PSZ_AMD_T_ENCODE / _DECODE are the FZG kernels.  Region decode takes
+ * PSZ_AMD_REGION_FALLBACK (psz_amd_region_plan says so).  psz_amd_merge_archives returns
+ * PSZ_ABORT_NO_SUCH_CODEC for FZG parts. */
 
 /* ---- sharded compress (multi-GPU; the reference has no multi-GPU path) ----
  * A field split into tile-aligned slabs (z: multiples of 8 planes) is compressed one slab per
