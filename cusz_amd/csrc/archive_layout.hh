@@ -68,6 +68,7 @@ struct PhfView {
   const uint32_t* bitstream;
   size_t bs_words;  // words from the bitstream's start to the archive's end (the range of the
                     // decoders' loads); 0 when entry[5] does not reach the bitstream
+  size_t bits_words;  // the bitstream's own cells (to the outlier cells at entry[3]); 0 likewise
   const uint8_t* revbook;
   const uint32_t* par_nbit;
   const uint32_t* par_entry;
@@ -87,6 +88,8 @@ struct PhfView {
     bits_rel = l.bits_rel;
     const size_t bits_off = phf_off + l.bits_rel, total = h->entry[PSZHEADER_ENC_PASS2_END];
     bs_words = total > bits_off ? (total - bits_off) / 4 : 0;
+    const size_t cells_off = h->entry[PSZHEADER_SPFMT];
+    bits_words = cells_off > bits_off ? (cells_off - bits_off) / 4 : 0;
   }
 };
 

@@ -1205,7 +1205,6 @@ k_brick1_decode(const uint32_t* __restrict__ bitstream, uint32_t bs_words, const
 // tile as codes (two rows of 128 B per store instruction).  Used for every archive (chunk length
 // a multiple of 64) the fused decoders do not take: 2-D, spline, the reference layout, a
 // standalone decode of the codes.
-template <int DUMMY>
 __global__ void __launch_bounds__(64 * kDecWaves)
 k_chunk_decode(const uint32_t* __restrict__ bitstream, uint32_t bs_words, const uint8_t* __restrict__ revbook,
                int bklen, const uint32_t* __restrict__ par_nbit, const uint32_t* __restrict__ par_entry,
@@ -1365,7 +1364,7 @@ int launch_brick_region(const BrickLaunch& L, const PhfView& v, T* out_box, doub
   return (int)hipGetLastError();
 }
 
-int launch_chunk_decode(const BrickLaunch& L, const PhfView& v, uint16_t* codes, size_t n, hipStream_t st)
+int launch_chunk_decode(uint32_t ncu, const PhfView& v, uint16_t* codes, size_t n, hipStream_t st)
 {
   const uint32_t nchunks = (uint32_t)v.pardeg, sublen = (uint32_t)v.sublen;
   if (v.bs_words >= (1ull << 30) || v.bklen < 1 || v.bklen > kMaxBklen || sublen % kBlk != 0 || sublen == 0)
@@ -1375,12 +1374,11 @@ int launch_chunk_decode(const BrickLaunch& L, const PhfView& v, uint16_t* codes,
   // ceil(units / nCU) decoding waves per workgroup, instead of 8 on a fifth of the chip; the
   // workgroup keeps 8 waves so the tables take no longer to build.
   const uint32_t units = (nchunks + 63) / 64;
-  const uint32_t ncu = L.ncu > 0 ? (uint32_t)L.ncu : 256u;
   const uint32_t wpb = std::min<uint32_t>(kDecWaves, (units + ncu - 1) / ncu);
   const size_t lds = (size_t)wpb * kD4Cells;
   const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(ncu, (units + wpb - 1) / wpb));
-  k_chunk_decode<0><<<grid, 64 * kDecWaves, lds, st>>>(v.bitstream, (uint32_t)v.bs_words, v.revbook, v.bklen, v.par_nbit,
-                                                       v.par_entry, codes, n, nchunks, sublen, wpb);
+  k_chunk_decode<<<grid, 64 * kDecWaves, lds, st>>>(v.bitstream, (uint32_t)v.bs_words, v.revbook, v.bklen, v.par_nbit,
+                                                    v.par_entry, codes, n, nchunks, sublen, wpb);
   return (int)hipGetLastError();
 }
 

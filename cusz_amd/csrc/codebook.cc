@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "archive_layout.hh"
+#include "codebook.hh"
 
 namespace cusz_amd {
 

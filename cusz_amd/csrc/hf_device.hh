@@ -1,4 +1,4 @@
-// cusz_amd/csrc/hf_device.hh -- device helpers shared by the Huffman kernels (huffman.hip)
+// cusz_amd/csrc/hf_device.hh -- device helpers shared by the Huffman kernels (hf_encode.hip, hf_decode.hip)
 // and the fused brick kernels (brick_*.hip): wave64 scans, MSB-first codeword packing into LDS
 // cells, and the canonical-code decode table.
 //

@@ -38,15 +38,20 @@ int launch_lorenzo_c(const T* in, size_t lx, size_t ly, size_t lz, double eb, in
                      const LorenzoGeom& g, uint16_t* codes, const OutlierSink& ol, uint32_t* hist,
                      int bklen, hipStream_t st, const HostPub& pub = HostPub{});
 
-// 1-D Lorenzo (non-ZigZag) reads the outlier values straight from the archive's cells when they
-// are in strictly increasing index order (this compressor's archives without spill): code 0 marks
-// exactly the outliers, so the k-th zero code of a brick takes the brick's k-th cell.  bstart
-// (nbricks + 1) and the unsorted flag come from launch_x1d_bounds; an unsorted list falls back
-// to the scatter (launch_scatter with only_if = unsorted) and reads from `out`.
-struct X1dOutliers {
-  const uint32_t* cells = nullptr;
+// The archive's outlier cells as the reconstructing kernels read them: straight from the archive,
+// grouped by brick, when a bounds pass found them in order; otherwise (*unsorted == epoch) the
+// scatter pass (launch_scatter with only_if = unsorted) has written the values into `out`, which
+// the kernels read instead.
+//  * 1-D Lorenzo (non-ZigZag): cells in strictly increasing index order (this compressor's
+//    archives without spill).  Code 0 marks exactly the outliers, so the k-th zero code of a
+//    brick takes the brick's k-th cell.  Bounds: launch_x1d_bounds.
+//  * the fused brick decoders: cells grouped by brick and sorted by (row, x) (this compressor
+//    writes them so); the decoder ranks the zero codes of each row against the brick's cells.
+//    Bounds: launch_brick_cell_bounds (3-D), launch_x1d_bounds over chunks (1-D).
+struct BrickOutliers {
+  const uint32_t* cells = nullptr;  // archive cells {f32 value, u32 idx}
   size_t ncell = 0;
-  const uint32_t* bstart = nullptr;
+  const uint32_t* bstart = nullptr;    // nbricks + 1
   const uint32_t* unsorted = nullptr;  // == epoch: unsorted (the flag word is never reset)
   uint32_t epoch = 0;
 };
@@ -56,13 +61,13 @@ int launch_x1d_bounds(const uint32_t* cells, size_t ncell, size_t n, uint32_t nb
 
 template <typename T>
 int launch_lorenzo_x(const uint16_t* codes, T* out, size_t lx, size_t ly, size_t lz, double eb, int radius,
-                     bool zigzag, const LorenzoGeom& g, hipStream_t st, const X1dOutliers* ox = nullptr);
+                     bool zigzag, const LorenzoGeom& g, hipStream_t st, const BrickOutliers* ox = nullptr);
 
 template <typename T>
 int launch_scatter(const uint32_t* cells, size_t nnz, T* out, size_t n, hipStream_t st,
                    const uint32_t* only_if = nullptr, uint32_t epoch = 0);
 
-// ---- Huffman (huffman.hip) ---------------------------------------------------------------
+// ---- Huffman, reference layout (hf_encode.hip, hf_decode.hip) -------------------------------
 struct HfEncodeArgs {
   const uint16_t* codes;
   size_t n;
@@ -73,36 +78,25 @@ struct HfEncodeArgs {
   uint32_t* par_nbit;    // archive segment
   uint32_t* par_entry;   // archive segment
   uint32_t* bitstream;   // archive segment (4-byte aligned)
-  unsigned long long* status;  // pardeg/kGroup+1 lookback words, zeroed before launch
-  unsigned int* timeout;       // set nonzero if a bounded spin gave up
-  uint32_t* temp;              // scratch of hf_encode_temp_words(); nullptr = look-back encoder
-  unsigned long long* total_nbit = nullptr;  // if set (zeroed before): the tile-sum pass adds every chunk's bits
-  uint32_t* ticket = nullptr;  // kPubTicketWords words zeroed per call: up to 2,048 tiles the tile-sum
-                               // launch's last workgroup scans them (k_hf_tile_scan not launched)
+  uint32_t* temp;              // scratch of hf_encode_temp_words()
+  uint32_t* ticket;            // kPubTicketWords words zeroed per call (the tile-sum launch's last workgroup
+                               // scans up to 2,048 tiles itself)
+  unsigned long long* total_nbit = nullptr;  // if set: the tile-sum pass writes the sum of every chunk's bits
 };
 int launch_hf_encode(const HfEncodeArgs& a, hipStream_t st);
 size_t hf_encode_temp_words(int sublen, int pardeg);
 
 // decode table scratch (u32 words): L1 4096 | maxl | first[] | bases | L2 2048, then a 32-B
-// sink the lane decoder stores to when it has nothing to flush (HfDecodeArgs::lut)
+// sink the lane decoder stores to when it has nothing to flush
 constexpr int kHfDecTableWords = 4096 + 128 + 2048;
 constexpr int kHfDecScratchWords = kHfDecTableWords + 16;
 
-struct HfDecodeArgs {  // its first five fields: a PhfView's (archive_layout.hh)
-  const uint32_t* bitstream;
-  const uint8_t* revbook;  // first i32[32] | entry i32[32] | keys u16[bklen]
-  int bklen;
-  const uint32_t* par_nbit;
-  const uint32_t* par_entry;
-  int sublen;
-  int pardeg;
-  size_t n;
-  uint16_t* out;
-  uint32_t* lut;     // scratch u32[kHfDecTableWords], 16-B aligned (built by the decode launch)
-  size_t avg_cells;  // average cells per chunk (sizes the LDS staging area); 0 = unknown
-  int decoder;       // PSZ_AMD_DECODER_* (0 auto)
-};
-int launch_hf_decode(const HfDecodeArgs& a, hipStream_t st);
+// The one chooser of the decoders that write codes in index order (chunk c's at codes[sublen c ...]):
+// the chunk decoder (launch_chunk_decode) when the knob is AUTO and it can read the archive, else
+// the LANE window decoder or the WAVE decoder (hf_decode.hip, which states the rule).
+// lut: scratch u32[kHfDecScratchWords], 16-B aligned; decoder: PSZ_AMD_DECODER_*; ncu: the device's CUs
+int launch_hf_decode(const PhfView& v, size_t n, uint16_t* codes, uint32_t* lut, int decoder, int ncu,
+                     hipStream_t st);
 
 // ---- FZG codec (fzg.hip): bit-plane shuffle + zero-word coder, archive_layout.hh FzgLayout ----
 // symbols: the codes (transform kFzgPlain) or zigzag(code - radius) (kFzgZigzagDelta)
@@ -364,22 +358,12 @@ int launch_brick_sample(const BrickLaunch& L, const T* in, double eb, int radius
 template <typename T>
 int launch_brick_stream(const BrickLaunch& L, const T* in, double eb, int radius, bool zz, const BrickSingle& s,
                         const void* psz_tpl, const void* phf_tpl, hipStream_t st, const HostPub& pub);
-// Outlier cells for the fused decoder: when the archive's cells are grouped by brick and sorted
-// by (row, x) (k_brick_cell_bounds checks; this compressor writes them so), the decoder ranks the
-// zero codes of each row against the brick's cells and no scatter pass is needed; otherwise
-// (*unsorted set) the scatter pass has written the values into `out`, which the decoder reads.
-struct BrickOutliers {
-  const uint32_t* cells = nullptr;  // archive cells {f32 value, u32 idx}
-  size_t ncell = 0;
-  const uint32_t* bstart = nullptr;   // nbricks + 1
-  const uint32_t* unsorted = nullptr;  // == epoch: unsorted (the flag word is never reset)
-  uint32_t epoch = 0;
-};
+// the fused decoders' outlier bounds (BrickOutliers above): k_brick_cell_bounds checks the order
 int launch_brick_cell_bounds(const BrickLaunch& L, const uint32_t* cells, size_t ncell, uint32_t* bstart,
                              uint32_t* unsorted, uint32_t epoch, hipStream_t st);
 // decode only, any archive whose chunk length is a multiple of 64: chunk c's codes to
-// codes[sublen c ...] (index order)
-int launch_chunk_decode(const BrickLaunch& L, const PhfView& v, uint16_t* codes, size_t n, hipStream_t st);
+// codes[sublen c ...] (index order); called through launch_hf_decode
+int launch_chunk_decode(uint32_t ncu, const PhfView& v, uint16_t* codes, size_t n, hipStream_t st);
 template <typename T>
 int launch_brick_decode(const BrickLaunch& L, const PhfView& v, T* out, double eb, int radius, bool zz,
                         const BrickOutliers& ol, hipStream_t st);

@@ -315,12 +315,12 @@ __device__ __forceinline__ void fuse_row(const uint16_t* __restrict__ codes, con
 
 template <typename T, bool ZZ>
 __global__ void __launch_bounds__(256)
-k_lorenzo_x1d(const uint16_t* __restrict__ codes, T* out, size_t n, T ebx2, T r, uint32_t nbricks, X1dOutliers ox)
+k_lorenzo_x1d(const uint16_t* __restrict__ codes, T* out, size_t n, T ebx2, T r, uint32_t nbricks, BrickOutliers ox)
 {
   constexpr int V = 4;  // the reference thread owns 4 consecutive elements (launch.hh:124-132)
   const int lane = threadIdx.x & 63;
   const uint32_t nw = gridDim.x * (blockDim.x >> 6);
-  // outlier values from the sorted cells (see X1dOutliers) instead of the scattered `out`
+  // outlier values from the sorted cells (see BrickOutliers) instead of the scattered `out`
   const bool fused = !ZZ && ox.cells && *ox.unsorted != ox.epoch;
   const uint64_t lt = (1ull << lane) - 1;
   for (uint32_t brick = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); brick < nbricks; brick += nw) {
@@ -705,13 +705,13 @@ int launch_lorenzo_c(const T* in, size_t lx, size_t ly, size_t lz, double eb, in
 
 template <typename T>
 int launch_lorenzo_x(const uint16_t* codes, T* out, size_t lx, size_t ly, size_t lz, double eb, int radius,
-                     bool zigzag, const LorenzoGeom& g, hipStream_t st, const X1dOutliers* ox)
+                     bool zigzag, const LorenzoGeom& g, hipStream_t st, const BrickOutliers* ox)
 {
   const T ebx2 = (T)(eb * 2);  // lrz_x.cuhip.inl:432
   const T r = (T)radius;
   const int grid = grid_for(g.nbricks);
   if (g.ndim == 1) {
-    const X1dOutliers o = ox ? *ox : X1dOutliers{};
+    const BrickOutliers o = ox ? *ox : BrickOutliers{};
     if (zigzag)
       k_lorenzo_x1d<T, true><<<grid, 256, 0, st>>>(codes, out, lx, ebx2, r, g.nbricks, o);
     else
@@ -761,9 +761,9 @@ template int launch_lorenzo_c<double>(const double*, size_t, size_t, size_t, dou
                                       const LorenzoGeom&, uint16_t*, const OutlierSink&, uint32_t*, int,
                                       hipStream_t, const HostPub&);
 template int launch_lorenzo_x<float>(const uint16_t*, float*, size_t, size_t, size_t, double, int, bool,
-                                     const LorenzoGeom&, hipStream_t, const X1dOutliers*);
+                                     const LorenzoGeom&, hipStream_t, const BrickOutliers*);
 template int launch_lorenzo_x<double>(const uint16_t*, double*, size_t, size_t, size_t, double, int, bool,
-                                      const LorenzoGeom&, hipStream_t, const X1dOutliers*);
+                                      const LorenzoGeom&, hipStream_t, const BrickOutliers*);
 template int launch_scatter<float>(const uint32_t*, size_t, float*, size_t, hipStream_t, const uint32_t*, uint32_t);
 template int launch_scatter<double>(const uint32_t*, size_t, double*, size_t, hipStream_t, const uint32_t*, uint32_t);
 

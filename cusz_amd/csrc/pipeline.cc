@@ -6,7 +6,7 @@
 //   compress:  [extrema (Rel)] -> predict+quantize+histogram+outliers (1 kernel)
 //              -> histogram D2H, host codebook, book/revbook H2D (the one host round trip
 //                 the reference algorithm needs: the codebook depends on the full histogram)
-//              -> Huffman encode straight into the archive (1 kernel, device look-back)
+//              -> Huffman encode into the archive (hf_encode.hip: pack, tile sums, gather)
 //              -> finalize: outlier compaction + headers written on device
 //              -> one 176-B header read-back (compress is synchronous, as in the reference)
 //   decompress: outlier scatter -> Huffman decode -> Lorenzo reconstruct (queued, no sync)
@@ -32,6 +32,7 @@
 #include <tuple>
 
 #include "archive_layout.hh"
+#include "codebook.hh"
 #include "common.hh"
 #include "cusz.h"
 #include "cusz_amd.h"
@@ -40,11 +41,6 @@
 #include "kernels.hh"
 
 namespace cusz_amd {
-
-int build_codebook(const uint32_t* hist, int bklen, uint32_t* book, uint8_t* revbook);
-int build_codebook_twoqueue(const uint32_t* hist, int bklen, uint32_t smooth, uint32_t* book, uint8_t* revbook);
-int hf_encode_groups(int sublen, int pardeg);
-size_t hf_encode_temp_words(int sublen, int pardeg);
 
 int report_hip_error(hipError_t e, const char* expr, const char* file, int line)
 {
@@ -182,6 +178,7 @@ struct Pipeline {
   size_t n = 0;
   int ndim = 1;
   int device = 0;
+  int ncu = 0;  // the device's compute units (init)
   hipStream_t stream = nullptr;
   int elem_bytes = 4;
 
@@ -231,9 +228,7 @@ struct Pipeline {
   DevBuf<uint32_t> d_brick_off;
   DevBuf<uint64_t> d_spill;
   DevBuf<SmallBuf> d_small;  // one SmallBuf
-  DevBuf<unsigned long long> d_status;
   DevBuf<uint32_t> d_enc_temp;     // encoder scratch (chunk cells at a worst-case stride)
-  size_t status_words = 0;
   DevBuf<uint8_t> d_archive;
   size_t archive_cap = 0;
 
@@ -312,6 +307,7 @@ struct Pipeline {
     if (ndim == 2 && l.x * (size_t)elem_bytes >= 0x80000000ull) return PSZ_ABORT_UNSUPPORTED_DIMENSION;
     stream = (hipStream_t)st;
     CUSZ_AMD_HIP_CHECK(hipGetDevice(&device));
+    CUSZ_AMD_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
     tune_chunking(n, device, &sublen, &pardeg);
     tuned_sublen = sublen;
     geom = lorenzo_geom(ndim, l.x, l.y, l.z, elem_bytes);
@@ -424,16 +420,12 @@ struct Pipeline {
 
   hipError_t alloc_chunk_state()
   {
-    d_status.free();
     d_enc_temp.free();
     if (const size_t tw = hf_encode_temp_words(sublen, pardeg)) {
       const hipError_t et = d_enc_temp.alloc(tw);
       if (et != hipSuccess) return et;
     }
     d_archive.free();
-    status_words = (size_t)hf_encode_groups(sublen, pardeg) + 1;
-    hipError_t e = d_status.alloc(status_words);
-    if (e != hipSuccess) return e;
     const size_t ol_cells = std::max(slot_cells_total(), (size_t)sgeom.ntiles * spl_cap);
     // chunk tables: the tuned chunking's, or the brick layout's (one chunk per brick row)
     const size_t chunks = std::max((size_t)pardeg, bl.g.ok ? (size_t)bl.g.nchunks : 0);
@@ -640,12 +632,11 @@ struct Pipeline {
     if (int fs = scale_rel_eb<T>(h, in)) return fs;
     const double eb = h->rc.eb;
 
-    // per-call state reset (the reference never resets these: SURVEY.md Appendix B.3); the third
-    // region: pass 1's codebook sample (bricks), else the encoder's look-back words
-    void* const z3 = brick ? (void*)d_shist.p : (void*)d_status.p;
-    const size_t z3_bytes = brick ? ((size_t)kMaxBklen * kSampleBinStride + 16) * 4 : status_words * 8;
-    CUSZ_AMD_HIP_CHECK((hipError_t)launch_zero(
-        regions({{d_hist, nullptr, (size_t)(bklen + 1) * 4}, {d_small, nullptr, kSmallZeroBytes}, {z3, nullptr, z3_bytes}}), stream));
+    // per-call state reset (the reference never resets these: SURVEY.md Appendix B.3); the brick
+    // path's third region: pass 1's codebook sample
+    const std::tuple<void*, const void*, size_t> zh{d_hist, nullptr, (size_t)(bklen + 1) * 4}, zs{d_small, nullptr, kSmallZeroBytes},
+        zb{d_shist, nullptr, ((size_t)kMaxBklen * kSampleBinStride + 16) * 4};
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_zero(brick ? regions({zh, zs, zb}) : regions({zh, zs}), stream));
     mark(1);
     last_layout = brick ? PSZ_AMD_LAYOUT_BRICK : PSZ_AMD_LAYOUT_REFERENCE;
     pend.brick = brick, pend.spl = spl, pend.radius = radius, pend.zz = zz, pend.fzg = fzg;
@@ -762,11 +753,9 @@ struct Pipeline {
                     reinterpret_cast<uint32_t*>(phf + lay.nbit_rel),
                     reinterpret_cast<uint32_t*>(phf + lay.entry_rel),
                     reinterpret_cast<uint32_t*>(phf + lay.bits_rel),
-                    d_status,
-                    timeout(),
-                    d_enc_temp};
-    ea.total_nbit = &info()->total_nbit;  // summed by the encoder's tile-sum pass
-    ea.ticket = plan_ticket();            // (the brick plan's ticket: unused on this path)
+                    d_enc_temp,
+                    plan_ticket(),  // (the brick plan's ticket: unused on this path)
+                    &info()->total_nbit};  // summed by the encoder's tile-sum pass
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_hf_encode(ea, stream));
     mark(4);
 
@@ -1089,18 +1078,7 @@ struct Pipeline {
       if (const int s = check_fzg(h, in, &fh)) return s;
       return decode_fzg(h, in, fh);
     }
-    const PhfView v(h, in);
-    const int pd = v.pardeg, sl = v.sublen;
-    if (sl % 64 == 0 && sl <= 8192 && decoder == 0 && pd > 0 && v.bklen <= kMaxBklen) {  // the fused decoders' chunk loop
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_chunk_decode(bl, v, d_codes, n, stream));
-      return PSZ_SUCCESS;
-    }
-    // average chunk size from the segment length (sizes the decoder's LDS staging)
-    const size_t seg = h->entry[PSZHEADER_ENCODED + 1] - h->entry[PSZHEADER_ENCODED];
-    const size_t avg_cells = pd > 0 && seg > v.bits_rel ? (seg - v.bits_rel) / 4 / (size_t)pd : 0;
-    const HfDecodeArgs da{v.bitstream, v.revbook, v.bklen, v.par_nbit, v.par_entry, sl,
-                          pd,          n,         d_codes, dec_lut(),  avg_cells,   decoder};
-    CUSZ_AMD_HIP_CHECK((hipError_t)launch_hf_decode(da, stream));
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_hf_decode(PhfView(h, in), n, d_codes, dec_lut(), decoder, ncu, stream));
     return PSZ_SUCCESS;
   }
 
@@ -1126,38 +1104,30 @@ struct Pipeline {
     const bool brickdec = !fzg && bl.g.ok && bl.g.ndim != 2 && decoder == 0 && h->vle_sublen == bl.g.W &&
                           2 * h->rc.radius <= kMaxBklen;
     const uint32_t* cells = reinterpret_cast<const uint32_t*>(in + h->entry[PSZHEADER_SPFMT]);
-    X1dOutliers ox;  // 1-D: the reconstruction reads sorted cells directly (no scatter pass)
-    if (geom.ndim == 1 && d_x1d && !zz && !brickdec && h->splen) {
-      const uint32_t nb = geom.nbricks;
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_x1d_bounds(cells, h->splen, n, nb, d_x1d, d_x1d + nb + 1,
-                                                       next_cell_epoch(), stream));
-      ox = X1dOutliers{cells, (size_t)h->splen, d_x1d, d_x1d + nb + 1, cell_epoch};
-    }
-    // fused brick path: the decoder ranks each row's zero codes against the brick's cells when
-    // they are grouped and sorted; only otherwise does the scatter below run (only_if = unsorted)
-    BrickOutliers bo;
-    if (brickdec && !zz && h->splen) {
-      // cells per brick (3-D) or per chunk (1-D)
-      const uint32_t nb = bl.g.ndim == 1 ? bl.g.nchunks : bl.g.nbricks;
-      if (bl.g.ndim == 1)
-        CUSZ_AMD_HIP_CHECK((hipError_t)launch_x1d_bounds(cells, h->splen, n, nb, d_x1d, d_x1d + nb + 1,
-                                                         next_cell_epoch(), stream, 8));
-      else
+    // The 1-D reconstruction and the fused brick decoders read sorted cells in place: the fused
+    // decoder ranks each row's zero codes against the brick's cells when they are grouped and
+    // sorted; only otherwise does the scatter below run (only_if = unsorted).
+    BrickOutliers ol;
+    if (!zz && h->splen && (brickdec || (geom.ndim == 1 && d_x1d))) {
+      // cells per reconstruction brick (1-D, not fused), per chunk (fused 1-D) or per brick (fused 3-D)
+      const uint32_t nb = !brickdec ? geom.nbricks : bl.g.ndim == 1 ? bl.g.nchunks : bl.g.nbricks;
+      if (brickdec && bl.g.ndim != 1)
         CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_cell_bounds(bl, cells, h->splen, d_x1d, d_x1d + nb + 1,
                                                                 next_cell_epoch(), stream));
-      bo = BrickOutliers{cells, (size_t)h->splen, d_x1d, d_x1d + nb + 1, cell_epoch};
-      ox.unsorted = bo.unsorted;
-      ox.epoch = cell_epoch;
+      else
+        CUSZ_AMD_HIP_CHECK((hipError_t)launch_x1d_bounds(cells, h->splen, n, nb, d_x1d, d_x1d + nb + 1,
+                                                         next_cell_epoch(), stream, brickdec ? 8 : 14));
+      ol = BrickOutliers{cells, (size_t)h->splen, d_x1d, d_x1d + nb + 1, cell_epoch};
     }
     if (zz) CUSZ_AMD_HIP_CHECK(hipMemsetAsync(out, 0, n * sizeof(T), stream));
-    CUSZ_AMD_HIP_CHECK((hipError_t)launch_scatter<T>(cells, h->splen, out, n, stream, ox.unsorted, ox.epoch));
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_scatter<T>(cells, h->splen, out, n, stream, ol.unsorted, ol.epoch));
     mark(7);
-    if (brickdec) return decompress_brick<T>(h, in, out, zz, bo);
+    if (brickdec) return decompress_brick<T>(h, in, out, zz, ol);
     int s = fzg ? decode_fzg(h, in, fh) : decode_codes(h, in);
     if (s) return s;
     mark(8);
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_lorenzo_x<T>(d_codes, out, len.x, len.y, len.z, h->rc.eb, h->rc.radius,
-                                                       zz, geom, stream, ox.cells ? &ox : nullptr));
+                                                       zz, geom, stream, ol.cells ? &ol : nullptr));
     mark(9);
     return PSZ_SUCCESS;
   }

@@ -1,5 +1,5 @@
 // Host emulation of the decode tables (k_hf_tables) and the lane-per-chunk decoder
-// (k_hf_decode_lane) in cusz_amd/csrc/huffman.hip, lane by lane, with bounds assertions.
+// (k_hf_decode_lane) in cusz_amd/csrc/hf_decode.hip, lane by lane, with bounds assertions.
 // Development tool: g++ -O2 -o lpc_sim lpc_sim.cc ; ./lpc_sim <dir>  (files written by lpc_sim.py)
 #include <cassert>
 #include <cstdint>

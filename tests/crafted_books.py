@@ -23,7 +23,7 @@ BKLEN = 1024
 LMAX = 27          # longest code a book word (code | len << 27) holds
 ROW = 256          # place()'s patterns are laid out over rows of 256 codes (a brick row)
 L1_BITS, L2_BITS = 12, 16
-# usable second-table entries: kL2Cap4 (hf_device.hh) = kL2Cap (huffman.hip) = 2048, whose last slot
+# usable second-table entries: kL2Cap4 (hf_device.hh) = kL2Cap (hf_decode.hip) = 2048, whose last slot
 # stays 0; 4095 is the same edge of a 4096-entry table, which no decoder has: kept as a second cap
 L2_CAPS = (2047, 4095)
 KLASS_L1, KLASS_L2, KLASS_LONG = 0, 1, 2

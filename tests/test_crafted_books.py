@@ -173,7 +173,7 @@ def test_bands_rows_run_at_the_extreme_rates(oracle, name):
 def test_sparse16_has_a_chunk_far_above_the_average(oracle, name):
     """deep27: the dense row is more than ten times the mean.  Both profiles: it is past the wave
     decoder's LDS staging (1.5 x the average chunk's cells + 64, rounded up to 16 cells:
-    huffman.hip launch_hf_decode), so that decoder reads it from global memory."""
+    hf_decode.hip launch_hf_decode), so that decoder reads it from global memory."""
     b = cb.book_of(name)
     nbit = oracle.hf_encode(cb.place(name, N3, "sparse16", SEED), b.book, 256)[0].astype(np.int64)
     if name == "deep27":

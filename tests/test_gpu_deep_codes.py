@@ -10,9 +10,11 @@ the archive from archive_util.oracle_archive, want = oracle.lorenzo_x; then psz_
 must return the input codes exactly, and decompress into a NaN-poisoned buffer must equal want bit
 for bit.
 
-Which kernel a row runs (pipeline.cc decode_codes: AUTO and sublen % 64 == 0 -> k_chunk_decode,
-else launch_hf_decode; decompress: AUTO, a brick-shaped field that is not 2-D and sublen 256 ->
-the fused brick decoders, whose reconstruction is then what the decompress checks):
+Which kernel a row runs (hf_decode.hip launch_hf_decode, the one chooser behind decode_codes: AUTO
+and sublen a multiple of 64, at most 8192 -> k_chunk_decode; else LANE (k_hf_decode_win) when
+sublen % 16 == 0 and the knob says LANE or, under AUTO, pardeg >= 64 per CU; else WAVE
+(k_hf_decode).  decompress: AUTO, a brick-shaped field that is not 2-D and sublen 256 -> the
+fused brick decoders, whose reconstruction is then what the decompress checks):
 
 | Kernel                  | Dims                                          | sublen          | Decoder                   |
 |-------------------------|-----------------------------------------------|-----------------|---------------------------|

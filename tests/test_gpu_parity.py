@@ -157,6 +157,22 @@ def test_parity_sublen_override(oracle, sublen):
     assert a["sublen"] == sublen
 
 
+def test_reference_layout_tile_scan_edge(oracle):
+    """The reference-layout encoder's scan of its per-tile cell totals (hf_encode.hip scan_tiles,
+    64 chunks a tile) on both sides of its threshold: 2^25 values in chunks of 256 are 131,072
+    chunks and 2,048 tiles, the most that k_hf_tile_sums' last workgroup scans itself; one value
+    more makes 2,049 tiles, which k_hf_tile_scan scans, and a final chunk of one symbol.  par_entry,
+    par_nbit and every chunk's cells are held to the oracle byte for byte, and all three decoders'
+    output bit for bit (run_roundtrip).  A smooth field with a few spikes: the outlier path is on."""
+    full = _field("smooth", ((1 << 25) + 1, 1, 1), np.float32, seed=25)
+    spikes = [0, 255, 256, 1 << 20, (1 << 24) + 7, (1 << 25) - 300]
+    full[spikes] += 100.0
+    for n in (1 << 25, (1 << 25) + 1):
+        arch, a = run_roundtrip(oracle, full[:n], (n, 1, 1), 1e-4, layout=cz.LAYOUT_REFERENCE, sublen=256)
+        assert a["sublen"] == 256 and a["pardeg"] == (n + 255) // 256
+        assert a["header"].splen >= len(spikes)
+
+
 @pytest.mark.parametrize("t,dims", [("t1", (256, 1, 1)), ("t2", (16, 16, 1)), ("t3", (8, 8, 8))])
 def test_reference_kat_on_gpu(oracle, t, dims):
     """The reference's own KATs (correctness.inl) through the GPU path (eb=0.5)."""
