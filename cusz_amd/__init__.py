@@ -86,7 +86,31 @@ class psz_amd_region_info(C.Structure):
                 ("chunks", C.c_size_t), ("elems", C.c_size_t)]
 
 
+class psz_data_summary(C.Structure):
+    _fields_ = [("min", C.c_double), ("max", C.c_double), ("rng", C.c_double), ("std", C.c_double),
+                ("avg", C.c_double)]
+
+
+class psz_statistics(C.Structure):
+    """The reference's quality report (include/cusz/type.h psz_statistics)."""
+    _fields_ = [("odata", psz_data_summary), ("xdata", psz_data_summary),
+                ("score_PSNR", C.c_double), ("score_MSE", C.c_double), ("score_NRMSE", C.c_double),
+                ("score_coeff", C.c_double), ("max_err_abs", C.c_double), ("max_err_rel", C.c_double),
+                ("max_err_pwrrel", C.c_double), ("max_err_idx", C.c_size_t), ("autocor_lag_one", C.c_double),
+                ("autocor_lag_two", C.c_double), ("user_eb", C.c_double), ("len", C.c_size_t)]
+
+
+class psz_amd_quality(C.Structure):
+    """What psz_amd_assess_quality_* fills (include/cusz_amd.h): stat over the finite pairs."""
+    _fields_ = [("stat", psz_statistics), ("n_finite", C.c_size_t), ("n_nonfinite", C.c_size_t),
+                ("n_unbounded", C.c_size_t), ("first_unbounded_idx", C.c_size_t), ("first_diff_idx", C.c_size_t)]
+
+
+SIZE_MAX = C.c_size_t(-1).value
+QUALITY_AUTOCOR = 1  # PSZ_AMD_QUALITY_AUTOCOR
+
 assert C.sizeof(psz_header) == 176, C.sizeof(psz_header)
+assert C.sizeof(psz_statistics) == 176 and C.sizeof(psz_amd_quality) == 216, C.sizeof(psz_amd_quality)
 
 # every symbol declared in include/*.h that the library defines
 EXPORTS = [
@@ -120,6 +144,8 @@ EXPORTS = [
     "psz_amd_merge_archives", "psz_amd_value_range",
     "psz_amd_region_plan", "psz_amd_decompress_region_float", "psz_amd_decompress_region_double",
     "psz_amd_last_region",
+    "psz_amd_assess_quality_float", "psz_amd_assess_quality_double", "psz_amd_assess_quality_region_float",
+    "psz_amd_assess_quality_region_double", "psz_amd_quality_merge",
 ]
 
 
@@ -192,6 +218,15 @@ def lib():
         fn.argtypes = [P, P, C.c_size_t, psz_len, psz_len, P]
     L.psz_amd_last_region.restype = C.c_int
     L.psz_amd_last_region.argtypes = [P, C.POINTER(psz_amd_region_info)]
+    for fn in (L.psz_amd_assess_quality_float, L.psz_amd_assess_quality_double):
+        fn.restype = C.c_int
+        fn.argtypes = [P, P, P, C.c_size_t, C.c_double, C.c_int, C.POINTER(psz_amd_quality)]
+    for fn in (L.psz_amd_assess_quality_region_float, L.psz_amd_assess_quality_region_double):
+        fn.restype = C.c_int
+        fn.argtypes = [P, P, P, psz_len, psz_len, psz_len, C.c_double, C.c_int, C.POINTER(psz_amd_quality)]
+    L.psz_amd_quality_merge.restype = C.c_int
+    L.psz_amd_quality_merge.argtypes = [C.POINTER(psz_amd_quality), C.POINTER(C.c_size_t), C.c_int,
+                                        C.POINTER(psz_amd_quality)]
     L.phf_coarse_tune.argtypes = [C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.pszheader_filesize.restype = C.c_size_t
     L.pszheader_filesize.argtypes = [C.POINTER(psz_header)]
@@ -329,6 +364,31 @@ class Resource:
             raise PszError(st, "psz_amd_last_region")
         return o
 
+    def assess_quality(self, d_x: int, d_o: int, n: int, eb: float = 0.0, autocor: bool = False) -> psz_amd_quality:
+        """psz_amd_assess_quality_*: the reconstruction d_x against the original d_o, n elements of the
+        manager's dtype each (device pointers, element alignment), in one pass on the manager's
+        stream; eb > 0 also counts the pairs beyond 1.001 eb; autocor fills the lag autocorrelations."""
+        L = lib()
+        f = L.psz_amd_assess_quality_float if self.dtype == F4 else L.psz_amd_assess_quality_double
+        q = psz_amd_quality()
+        st = f(self._h, C.c_void_p(d_x), C.c_void_p(d_o), n, eb, QUALITY_AUTOCOR if autocor else 0, C.byref(q))
+        if st != PSZ_SUCCESS:
+            raise PszError(st, "psz_amd_assess_quality")
+        return q
+
+    def assess_quality_region(self, d_xbox: int, d_ofield: int, field_dims, origin, extent, eb: float = 0.0,
+                              autocor: bool = False) -> psz_amd_quality:
+        """psz_amd_assess_quality_region_*: a compact box (what decompress_region wrote) against the
+        same box of the whole original field; indices are those of the box."""
+        L = lib()
+        f = L.psz_amd_assess_quality_region_float if self.dtype == F4 else L.psz_amd_assess_quality_region_double
+        q = psz_amd_quality()
+        st = f(self._h, C.c_void_p(d_xbox), C.c_void_p(d_ofield), _len3(field_dims), _origin3(origin), _len3(extent),
+               eb, QUALITY_AUTOCOR if autocor else 0, C.byref(q))
+        if st != PSZ_SUCCESS:
+            raise PszError(st, "psz_amd_assess_quality_region")
+        return q
+
     def set_header(self, h: psz_header):
         lib().psz_modify_resource_manager_from_header(self._h, C.byref(h))
 
@@ -419,6 +479,18 @@ def merge_archives(parts, full_dims, offsets=None) -> bytes:
     if st != PSZ_SUCCESS:
         raise PszError(st, "psz_amd_merge_archives")
     return out.raw[: need.value]
+
+
+def quality_merge(parts, offsets) -> psz_amd_quality:
+    """psz_amd_quality_merge (host only): the statistics of a field from those of its consecutive
+    parts; offsets[i] is the element at which part i starts."""
+    arr = (psz_amd_quality * len(parts))(*parts)
+    offs = (C.c_size_t * len(parts))(*[int(o) for o in offsets])
+    out = psz_amd_quality()
+    st = lib().psz_amd_quality_merge(arr, offs, len(parts), C.byref(out))
+    if st != PSZ_SUCCESS:
+        raise PszError(st, "psz_amd_quality_merge")
+    return out
 
 
 def coarse_tune(n: int):

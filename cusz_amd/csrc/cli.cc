@@ -81,32 +81,38 @@ static bool parse_region(const char* s, psz_len* origin, psz_len* extent)
   return true;
 }
 
-// the same box of a whole field on the host (the --origin comparison of a region decode)
-template <typename T>
-static std::vector<T> crop(const T* f, psz_len l, psz_len o, psz_len e)
+// --origin FILE: the original is uploaded and compared with the reconstruction on the device
+// (psz_amd_assess_quality_*; the region variant for a box).  Two lines: the bound and the scores,
+// then where the worst element is and how many break the bound.
+static int report_quality(psz_resource* m, const psz_header& h, const char* path, const void* d_out, bool region,
+                          psz_len origin, psz_len extent)
 {
-  std::vector<T> b(e.x * e.y * e.z);
-  for (size_t z = 0; z < e.z; z++)
-    for (size_t y = 0; y < e.y; y++)
-      std::memcpy(&b[(z * e.y + y) * e.x], f + ((o.z + z) * l.y + o.y + y) * l.x + o.x, e.x * sizeof(T));
-  return b;
-}
-
-template <typename T>
-static void quality(const T* a, const T* b, size_t n, double eb)
-{
-  double maxe = 0, mn = INFINITY, mx = -INFINITY, se = 0;
-  for (size_t i = 0; i < n; i++) {
-    double d = std::fabs((double)a[i] - (double)b[i]);
-    maxe = d > maxe ? d : maxe;
-    se += d * d;
-    mn = a[i] < mn ? a[i] : mn;
-    mx = a[i] > mx ? a[i] : mx;
+  const size_t n = h.len.x * h.len.y * h.len.z, es = h.dtype == F8 ? 8 : 4;
+  std::vector<char> orig;
+  if (!read_file(path, orig) || orig.size() < n * es) {  // no report, as before
+    std::fprintf(stderr, "[cusz] --origin: cannot read %zu bytes from %s\n", n * es, path);
+    return 0;
   }
-  const double rng = mx - mn, mse = se / (double)n;
-  const double psnr = 20 * std::log10(rng) - 10 * std::log10(mse);
-  std::printf("max-error %.6e (eb %.6e, %s), PSNR %.3f dB, NRMSE %.6e\n", maxe, eb,
-              maxe <= eb * 1.001 ? "bounded" : "NOT bounded", psnr, std::sqrt(mse) / rng);
+  void* d_orig;
+  CK(hipMalloc(&d_orig, n * es));
+  CK(hipMemcpy(d_orig, orig.data(), n * es, hipMemcpyHostToDevice));
+  psz_amd_quality q;
+  const double eb = h.rc.eb;
+  int s;
+  if (h.dtype == F4)
+    s = region ? psz_amd_assess_quality_region_float(m, (const float*)d_out, (const float*)d_orig, h.len, origin, extent, eb, 0, &q)
+               : psz_amd_assess_quality_float(m, (const float*)d_out, (const float*)d_orig, n, eb, 0, &q);
+  else
+    s = region ? psz_amd_assess_quality_region_double(m, (const double*)d_out, (const double*)d_orig, h.len, origin, extent, eb, 0, &q)
+               : psz_amd_assess_quality_double(m, (const double*)d_out, (const double*)d_orig, n, eb, 0, &q);
+  CK(hipFree(d_orig));
+  if (s != PSZ_SUCCESS) return std::fprintf(stderr, "[cusz] quality assessment failed with status %d\n", s), 1;
+  std::printf("max-error %.6e (eb %.6e, %s), PSNR %.3f dB, NRMSE %.6e\n", q.stat.max_err_abs, eb,
+              q.n_unbounded == 0 ? "bounded" : "NOT bounded", q.stat.score_PSNR, q.stat.score_NRMSE);
+  const std::string first = q.first_unbounded_idx == SIZE_MAX ? "none" : std::to_string(q.first_unbounded_idx);
+  std::printf("coeff %.9f, max_err_idx %zu, n_unbounded %zu, first_unbounded_idx %s, n_nonfinite %zu\n", q.stat.score_coeff,
+              q.stat.max_err_idx, q.n_unbounded, first.c_str(), q.n_nonfinite);
+  return 0;
 }
 
 // --dump hist,quant (compressor.inl:507-529): the histogram u32[2r] and the quant codes
@@ -269,15 +275,7 @@ int main(int argc, char** argv)
                   r_origin.x, r_origin.y, r_origin.z, r_extent.x, r_extent.y, r_extent.z, ctx->cli->file_input,
                   base.c_str(), nb * es, ri.path == PSZ_AMD_REGION_FUSED ? "fused" : "fallback", ri.bricks);
       if (ctx->cli->report_time) std::printf("time: region decompress %.3f ms (wall)\n", wall);
-      if (ctx->cli->file_compare[0]) {
-        std::vector<char> orig;
-        if (read_file(ctx->cli->file_compare, orig) && orig.size() >= n * es) {
-          if (h.dtype == F4)
-            quality(crop((const float*)orig.data(), h.len, r_origin, r_extent).data(), (const float*)out.data(), nb, h.rc.eb);
-          else
-            quality(crop((const double*)orig.data(), h.len, r_origin, r_extent).data(), (const double*)out.data(), nb, h.rc.eb);
-        }
-      }
+      if (ctx->cli->file_compare[0] && report_quality(m, h, ctx->cli->file_compare, d_out, true, r_origin, r_extent)) return 1;
       psz_release_resource(m);
       CK(hipFree(d_arch));
       CK(hipFree(d_out));
@@ -302,13 +300,7 @@ int main(int argc, char** argv)
     if (ctx->cli->report_time)
       std::printf("time: decompress %.3f ms (device %.3f ms) %.2f GB/s\n", wall, ms[PSZ_AMD_T_DECOMPRESS],
                   n * es / (ms[PSZ_AMD_T_DECOMPRESS] * 1e6));
-    if (ctx->cli->file_compare[0]) {
-      std::vector<char> orig;
-      if (read_file(ctx->cli->file_compare, orig) && orig.size() >= n * es) {
-        if (h.dtype == F4) quality((const float*)orig.data(), (const float*)out.data(), n, h.rc.eb);
-        else quality((const double*)orig.data(), (const double*)out.data(), n, h.rc.eb);
-      }
-    }
+    if (ctx->cli->file_compare[0] && report_quality(m, h, ctx->cli->file_compare, d_out, false, r_origin, r_extent)) return 1;
     psz_release_resource(m);
     CK(hipFree(d_arch));
     CK(hipFree(d_out));

@@ -388,4 +388,16 @@ int launch_crop_box(const T* field, size_t lx, size_t ly, const size_t (&o)[3], 
 template <typename T>
 int launch_extrema(const T* in, size_t n, double* d_minmax, unsigned int* d_scratch, hipStream_t st);
 
+// ---- quality assessment (quality.hip; record and combine: quality_reduce.hh) -----------------
+// One pass over reconstruction x and original o, then one small combine launch.  parts: device
+// QrPart[kQrGridCap + 1], the workgroups' records and, last, the result.  thr: 1.001 eb, +inf for
+// eb == 0.  The grid is qr_grid(len) / qr_region_grid(rows): the combine order depends on nothing else.
+struct QrPart;
+template <typename T>
+int launch_quality(const T* x, const T* o, size_t len, double thr, bool autocor, QrPart* parts, hipStream_t st);
+// x: the compact box of e elements; field: the whole original (lx, ly its x and y extents), box at o
+template <typename T>
+int launch_quality_region(const T* xbox, const T* field, size_t lx, size_t ly, const size_t (&o)[3],
+                          const size_t (&e)[3], double thr, bool autocor, QrPart* parts, hipStream_t st);
+
 }  // namespace cusz_amd

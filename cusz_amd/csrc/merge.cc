@@ -22,6 +22,7 @@
 
 #include "archive_layout.hh"
 #include "cusz_amd.h"
+#include "quality_reduce.hh"
 
 namespace {
 
@@ -176,5 +177,27 @@ extern "C" int psz_amd_merge_archives(const uint8_t* const* parts, const size_t*
     }
     cell_base += nc, chunk_base += pd, ol_base += p.h.splen, elem_base += p.n;
   }
+  return PSZ_SUCCESS;
+}
+
+// The statistics of a field from those of its consecutive parts: each part's record rebuilt from
+// its struct (quality_reduce.hh qr_from_quality), combined in part order as the kernel combines.
+extern "C" int psz_amd_quality_merge(const psz_amd_quality* parts, const size_t* elem_offsets, int nparts,
+                                     psz_amd_quality* out)
+{
+  using namespace cusz_amd;
+  if (!parts || !elem_offsets || !out || nparts < 1) return PSZ_AMD_ERR_INVALID_ARG;
+  size_t len = 0;
+  for (int i = 0; i < nparts; i++) {
+    const psz_amd_quality& q = parts[i];
+    if (elem_offsets[i] != len || q.stat.len == 0 || q.n_finite > q.stat.len ||
+        q.n_nonfinite != q.stat.len - q.n_finite || std::memcmp(&q.stat.user_eb, &parts[0].stat.user_eb, 8))
+      return PSZ_AMD_ERR_INVALID_ARG;
+    len += q.stat.len;
+  }
+  QrPart acc;
+  qr_part_init(acc);
+  for (int i = 0; i < nparts; i++) qr_combine(acc, qr_from_quality(parts[i], elem_offsets[i]));
+  qr_to_quality(acc, len, parts[0].stat.user_eb, false, out);
   return PSZ_SUCCESS;
 }

@@ -39,6 +39,7 @@
 #include "cusz_rev1.h"
 #include "hf.h"
 #include "kernels.hh"
+#include "quality_reduce.hh"
 
 namespace cusz_amd {
 
@@ -205,6 +206,7 @@ struct Pipeline {
   uint32_t cell_epoch = 0;        // tags the unsorted flag of the current decompress (never 0)
   uint32_t next_cell_epoch() { return cell_epoch = cell_epoch + 1 ? cell_epoch + 1 : 1; }
   DevBuf<uint8_t> d_region_field;  // region fallback: the whole field (allocated on first use)
+  DevBuf<QrPart> d_quality;        // quality assessment: workgroup records + the result (allocated on first use)
   psz_amd_region_info last_region{};
   bool has_last_region = false;
   size_t spl_x_words = 0;
@@ -1445,6 +1447,72 @@ int psz_amd_compress_finish(psz_resource* m, const uint32_t* d_hist, psz_header*
   const int s = p->compress_finish(m->header, d_hist, out, outlen);
   if (out_h) *out_h = *m->header;
   return s;
+}
+
+}  // extern "C"
+
+// Quality assessment (include/cusz_amd.h): one pass + one combine launch on the manager's stream,
+// one wait for the 232-byte record, the struct finished on the host (quality_reduce.hh).  Touches
+// no compress or decompress state.  box: field extents, origin, extent (the region variant).
+template <typename T>
+static int assess_quality_impl(psz_resource* m, const T* x, const T* o, size_t len, const psz_len* box, double eb,
+                               int flags, psz_amd_quality* out)
+{
+  Pipeline* p = cusz_amd::P(m);
+  if (!p || !x || !o || !out || !(eb >= 0.0) || (flags & ~PSZ_AMD_QUALITY_AUTOCOR)) return PSZ_AMD_ERR_INVALID_ARG;
+  if (box) {
+    const psz_len l = box[0], org = box[1], e = box[2];
+    if (!l.x || !l.y || !l.z || !e.x || !e.y || !e.z || org.x >= l.x || e.x > l.x - org.x || org.y >= l.y ||
+        e.y > l.y - org.y || org.z >= l.z || e.z > l.z - org.z)
+      return PSZ_AMD_ERR_INVALID_ARG;
+    len = e.x * e.y * e.z;
+  }
+  if (len == 0) return PSZ_AMD_ERR_INVALID_ARG;
+  CUSZ_AMD_HIP_CHECK(hipSetDevice(p->device));
+  if (!p->d_quality) CUSZ_AMD_HIP_CHECK(p->d_quality.alloc(cusz_amd::kQrGridCap + 1));
+  const bool ac = (flags & PSZ_AMD_QUALITY_AUTOCOR) != 0;
+  const double thr = eb > 0.0 ? 1.001 * eb : INFINITY;
+  if (box) {
+    const size_t o3[3] = {box[1].x, box[1].y, box[1].z}, e3[3] = {box[2].x, box[2].y, box[2].z};
+    CUSZ_AMD_HIP_CHECK((hipError_t)cusz_amd::launch_quality_region<T>(x, o, box[0].x, box[0].y, o3, e3, thr, ac,
+                                                                       p->d_quality, p->stream));
+  }
+  else
+    CUSZ_AMD_HIP_CHECK((hipError_t)cusz_amd::launch_quality<T>(x, o, len, thr, ac, p->d_quality, p->stream));
+  cusz_amd::QrPart part;
+  CUSZ_AMD_HIP_CHECK(hipMemcpyAsync(&part, p->d_quality.p + cusz_amd::kQrGridCap, sizeof(part), hipMemcpyDeviceToHost,
+                                    p->stream));
+  CUSZ_AMD_HIP_CHECK(hipStreamSynchronize(p->stream));
+  cusz_amd::qr_to_quality(part, len, eb, ac, out);
+  return PSZ_SUCCESS;
+}
+
+extern "C" {
+
+int psz_amd_assess_quality_float(psz_resource* m, const float* x, const float* o, size_t len, double eb, int flags,
+                                 psz_amd_quality* out)
+{
+  return assess_quality_impl<float>(m, x, o, len, nullptr, eb, flags, out);
+}
+
+int psz_amd_assess_quality_double(psz_resource* m, const double* x, const double* o, size_t len, double eb, int flags,
+                                  psz_amd_quality* out)
+{
+  return assess_quality_impl<double>(m, x, o, len, nullptr, eb, flags, out);
+}
+
+int psz_amd_assess_quality_region_float(psz_resource* m, const float* xbox, const float* ofield, psz_len field_len,
+                                        psz_len origin, psz_len extent, double eb, int flags, psz_amd_quality* out)
+{
+  const psz_len box[3] = {field_len, origin, extent};
+  return assess_quality_impl<float>(m, xbox, ofield, 0, box, eb, flags, out);
+}
+
+int psz_amd_assess_quality_region_double(psz_resource* m, const double* xbox, const double* ofield, psz_len field_len,
+                                         psz_len origin, psz_len extent, double eb, int flags, psz_amd_quality* out)
+{
+  const psz_len box[3] = {field_len, origin, extent};
+  return assess_quality_impl<double>(m, xbox, ofield, 0, box, eb, flags, out);
 }
 
 }  // extern "C"

@@ -249,6 +249,72 @@ int psz_amd_decompress_region_double(psz_resource* m, uint8_t* IN_d_compressed, 
  * checks); PSZ_AMD_ERR_STATE before the first one. */
 int psz_amd_last_region(psz_resource* m, psz_amd_region_info* out);
 
+/* ---- quality assessment on the device (the reference's GPU_assess_quality, GPU_find_max_error,
+ * GPU_error_bounded and GPU_identical, psz/include/detail/compare.hh, in one pass) ----
+ * Fills the reference's psz_statistics (cusz/type.h) for a reconstruction x against an original o,
+ * both device arrays of len elements of the suffix's type, each read once.  o and x are converted
+ * to double (exact), e_i = |x_i - o_i| is one double operation, and everything in `stat` runs
+ * over the finite pairs (both values finite; m = n_finite of them):
+ *   odata / xdata: min, max, rng = max - min, avg, std = sqrt(sum (v - avg)^2 / m)
+ *   max_err_abs = max e_i; max_err_idx = the lowest index that attains it (a region call: an index
+ *     into the compact box); max_err_rel = max_err_abs / odata.rng;
+ *     max_err_pwrrel = max e_i / |o_i| over o_i != 0 (NaN when there is none)
+ *   score_MSE = sum e^2 / m; score_NRMSE = sqrt(MSE) / odata.rng;
+ *     score_PSNR = 20 log10(odata.rng) - 10 log10(MSE)
+ *   score_coeff = (sum (o - avg_o)(x - avg_x) / m) / (std_o std_x)
+ *   user_eb = eb, len = len
+ *   autocor_lag_k (k = one, two): with PSZ_AMD_QUALITY_AUTOCOR the same correlation between
+ *     o[0 .. len - k) and o[k .. len) over their finite pairs; NaN without the flag or when none.
+ * Degenerate inputs take what IEEE gives: MSE 0 makes PSNR +inf, a zero std makes the coefficient
+ * NaN, n_finite == 0 makes every double of stat NaN (user_eb aside) and the indices SIZE_MAX.
+ * xdata.max is the reconstruction's and the error is kept in double (the reference's CPU path,
+ * compare.stl.inl:89 and :92, takes the former from odata and rounds the latter to float).
+ *
+ * Means, variances and the covariance come from per-lane shifted sums combined pairwise (Chan et
+ * al.), never from sum v^2 / n - mean^2; no floating-point atomics: two calls on the same inputs
+ * return byte-identical structs.
+ *
+ * The manager supplies the stream and a scratch buffer for partial records, allocated on the first
+ * quality call (never by compress or decompress).  len is any value >= 1, whatever the manager's
+ * field and dtype; the pointers need element alignment only.  The call queues on the manager's
+ * stream, waits once for the result and writes OUT_host.  It only reads: a pending
+ * psz_amd_compress_scan_* stays valid.  PSZ_AMD_ERR_INVALID_ARG, OUT_host untouched: a null handle
+ * or pointer, len == 0, eb negative or NaN, unknown flag bits, an empty box or one that leaves
+ * the field. */
+#define PSZ_AMD_QUALITY_AUTOCOR 1 /* also fill autocor_lag_one / _two (else NaN) */
+
+typedef struct psz_amd_quality {
+  psz_statistics stat;        /* the reference's struct, every field filled */
+  size_t n_finite;            /* pairs with both values finite: everything in stat is over these */
+  size_t n_nonfinite;         /* len - n_finite */
+  size_t n_unbounded;         /* pairs with |x - o| > 1.001 * eb (the reference's CPU_error_bounded rule),
+                                 plus non-finite pairs whose bit patterns differ; 0 when eb == 0 */
+  size_t first_unbounded_idx; /* lowest such index, SIZE_MAX when none */
+  size_t first_diff_idx;      /* lowest index whose bit patterns differ (GPU_identical), SIZE_MAX when identical */
+} psz_amd_quality;
+
+int psz_amd_assess_quality_float(psz_resource* m, const float* IN_d_xdata, const float* IN_d_odata, size_t len,
+                                 double eb, int flags, psz_amd_quality* OUT_host);
+int psz_amd_assess_quality_double(psz_resource* m, const double* IN_d_xdata, const double* IN_d_odata, size_t len,
+                                  double eb, int flags, psz_amd_quality* OUT_host);
+/* A compact box (what psz_amd_decompress_region_* wrote: extent elements, x fastest) against the
+ * same box of the whole original field of field_len elements.  Indices and the autocorrelation are
+ * those of the box as one array of extent.x * extent.y * extent.z elements. */
+int psz_amd_assess_quality_region_float(psz_resource* m, const float* IN_d_xbox, const float* IN_d_ofield,
+                                        psz_len field_len, psz_len origin, psz_len extent, double eb, int flags,
+                                        psz_amd_quality* OUT_host);
+int psz_amd_assess_quality_region_double(psz_resource* m, const double* IN_d_xbox, const double* IN_d_ofield,
+                                         psz_len field_len, psz_len origin, psz_len extent, double eb, int flags,
+                                         psz_amd_quality* OUT_host);
+/* Host only: the statistics of a field from those of its consecutive parts (the slabs of a sharded
+ * run), parts[i] starting at element elem_offsets[i] = the sum of the lengths before it
+ * (PSZ_AMD_ERR_INVALID_ARG otherwise, and for parts of different user_eb).  Each part's record is
+ * rebuilt from its n_finite, avg, std, score_coeff and score_MSE and combined as the kernel
+ * combines; indices are moved by the offsets, ties go to the lowest index.  The autocorrelations
+ * of a field do not follow from those of its parts: they are NaN. */
+int psz_amd_quality_merge(const psz_amd_quality* parts, const size_t* elem_offsets, int nparts,
+                          psz_amd_quality* out);
+
 const char* psz_amd_version(void);
 
 /* The device codebook (no host round trip; NOT the reference's heap order, the same total bit
