@@ -118,7 +118,7 @@ k_lorenzo_c1d(const T* __restrict__ in, size_t n, T ebx2_r, T r, uint16_t* __res
     if (lane == 0) ol.brick_cnt[brick] = cnt;
   }
   hist_flush(s_hist, g_hist, bklen);
-  publish_last(pub);  // the histogram to the host (pipeline.cc compress_scan)
+  publish_last(pub);  // the histogram to the host (pipeline_compress.cc compress_scan)
 }
 
 // 2D: brick = (64V) x 32 rows (one tile row); tiles 32 wide.
@@ -174,7 +174,7 @@ k_lorenzo_c2d(const T* __restrict__ in, uint32_t lx, uint32_t ly, T ebx2_r, T r,
     if (lane == 0) ol.brick_cnt[brick] = cnt;
   }
   hist_flush(s_hist, g_hist, bklen);
-  publish_last(pub);  // the histogram to the host (pipeline.cc compress_scan)
+  publish_last(pub);  // the histogram to the host (pipeline_compress.cc compress_scan)
 }
 
 // 3D: brick = (64V) x 8 x 8 (8V tiles of 8^3 along x).
@@ -235,7 +235,7 @@ k_lorenzo_c3d(const T* __restrict__ in, uint32_t lx, uint32_t ly, uint32_t lz, T
     if (lane == 0) ol.brick_cnt[brick] = cnt;
   }
   hist_flush(s_hist, g_hist, bklen);
-  publish_last(pub);  // the histogram to the host (pipeline.cc compress_scan)
+  publish_last(pub);  // the histogram to the host (pipeline_compress.cc compress_scan)
 }
 
 // =========================================================================================

@@ -19,7 +19,7 @@ import numpy as np
 
 from cusz_amd import datagen
 
-# ---- brick geometry (cusz_amd/csrc/brick_scan.hip brick_geom, pipeline.cc init) ----------------------
+# ---- brick geometry (cusz_amd/csrc/brick_scan.hip brick_geom, pipeline.cc Pipeline::init) ----------------------
 BRICK_X, BRICK_Y, BRICK_Z = 256, 8, 8       # a 3-D brick
 BRICK_ELEMS = BRICK_X * BRICK_Y * BRICK_Z   # also a linear (1-D, 2-D) brick's consecutive elements
 STREAM_SLOTS = 8                            # single-pass mode: one slot per y-step of a brick

@@ -22,13 +22,13 @@ CODE_LIM = (1 << 31) - 1024  # |code / 2| below this (spline.hip kSplCodeLim, :4
 
 
 def slot_cap(dims):
-    """Outlier cells a tile's slot holds (pipeline.cc init: spl_cap, :322)."""
+    """Outlier cells a tile's slot holds (pipeline.cc Pipeline::init: spl_cap)."""
     x, y, z = dims
     return min(x, 32) * min(y, 8) * min(z, 8) // 10 + 16
 
 
 def spill_cap(n):
-    """Cells of the shared spill list before any growth (pipeline.cc init: spill_cap, :326)."""
+    """Cells of the shared spill list before any growth (pipeline.cc Pipeline::init: spill_cap)."""
     return n // 10 + 1024
 
 

@@ -17,7 +17,7 @@ ids = lambda s: "x".join(map(str, s))  # noqa: E731
 
 def test_slot_geometry():
     assert ef.BRICK_ELEMS == 256 * 8 * 8 and SLOT == ef.BRICK_ELEMS // 10 + 16 and STEP == SLOT // 8
-    assert (SLOT, STEP) == (1654, 206)  # the figures DESIGN.md and pipeline.cc quote
+    assert (SLOT, STEP) == (1654, 206)  # the figures DESIGN.md quotes (pipeline.hh brick_slot_cap, kStreamSlots)
 
 
 @pytest.fixture(scope="module")

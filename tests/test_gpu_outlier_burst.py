@@ -1,7 +1,7 @@
 """Outlier bursts on the brick path: a y-step, a brick, or every brick of a field past its outlier
 slot (edge_fields.burst_field; test_edge_fields.py checks that each field overflows what it is
 meant to).  A slot that overflows sends cells to the shared spill list, the slots grow and the
-compress repeats (pipeline.cc grow_slots, finish_compress); what the caller gets must be the
+compress repeats (pipeline.cc grow_slots, pipeline_compress.cc finish_compress); what the caller gets must be the
 archive a manager with roomy slots writes: bit-exact parity with the oracle (codes, outlier set
 and values, histogram, Huffman segment, every decoder), the same bytes from the grown manager
 again and from a fresh one, cells in brick order (the fused region decoder reads them ranked).
