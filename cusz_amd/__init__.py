@@ -143,7 +143,7 @@ EXPORTS = [
     "psz_amd_compress_scan_float", "psz_amd_compress_scan_double", "psz_amd_compress_finish",
     "psz_amd_merge_archives", "psz_amd_value_range",
     "psz_amd_region_plan", "psz_amd_decompress_region_float", "psz_amd_decompress_region_double",
-    "psz_amd_last_region",
+    "psz_amd_last_region", "psz_amd_region_plan_mode", "psz_amd_set_region_mode",
     "psz_amd_assess_quality_float", "psz_amd_assess_quality_double", "psz_amd_assess_quality_region_float",
     "psz_amd_assess_quality_region_double", "psz_amd_quality_merge",
 ]
@@ -213,6 +213,11 @@ def lib():
     L.psz_amd_last_create_status.restype = C.c_int
     L.psz_amd_region_plan.restype = C.c_int
     L.psz_amd_region_plan.argtypes = [C.POINTER(psz_header), psz_len, psz_len, C.POINTER(psz_amd_region_info)]
+    L.psz_amd_region_plan_mode.restype = C.c_int
+    L.psz_amd_region_plan_mode.argtypes = [C.POINTER(psz_header), psz_len, psz_len, C.c_int,
+                                           C.POINTER(psz_amd_region_info)]
+    L.psz_amd_set_region_mode.restype = C.c_int
+    L.psz_amd_set_region_mode.argtypes = [P, C.c_int]
     for fn in (L.psz_amd_decompress_region_float, L.psz_amd_decompress_region_double):
         fn.restype = C.c_int
         fn.argtypes = [P, P, C.c_size_t, psz_len, psz_len, P]
@@ -239,7 +244,8 @@ DECODER_AUTO, DECODER_LANE, DECODER_WAVE = 0, 1, 2
 # archive layout (PSZ_AMD_LAYOUT_*)
 LAYOUT_BRICK, LAYOUT_REFERENCE, LAYOUT_BRICK_FORCE = 0, 1, 2
 CODEBOOK_EXACT, CODEBOOK_SAMPLED, CODEBOOK_STREAM = 0, 1, 2  # PSZ_AMD_CODEBOOK_*
-REGION_FUSED, REGION_FALLBACK = 0, 1  # PSZ_AMD_REGION_*
+REGION_FUSED, REGION_FALLBACK, REGION_SLAB = 0, 1, 2  # PSZ_AMD_REGION_*
+REGION_MODE_WHOLE, REGION_MODE_COVER = 0, 1  # PSZ_AMD_REGION_MODE_*
 
 
 def _len3(v) -> psz_len:
@@ -252,11 +258,12 @@ def _origin3(v) -> psz_len:
     return psz_len(x, y, z)
 
 
-def region_plan(header: psz_header, origin, extent) -> psz_amd_region_info:
-    """psz_amd_region_plan: host only; the path and the covering bricks of a box (origin, extent in
-    elements, x first) of an archive with this header.  PszError for a box outside the field."""
+def region_plan(header: psz_header, origin, extent, mode: int = REGION_MODE_WHOLE) -> psz_amd_region_info:
+    """psz_amd_region_plan_mode: host only; the path and the covering bricks or chunks of a box
+    (origin, extent in elements, x first) of an archive with this header, for a manager in `mode`
+    (REGION_MODE_*).  PszError for a box outside the field or an unknown mode."""
     o = psz_amd_region_info()
-    st = lib().psz_amd_region_plan(C.byref(header), _origin3(origin), _len3(extent), C.byref(o))
+    st = lib().psz_amd_region_plan_mode(C.byref(header), _origin3(origin), _len3(extent), mode, C.byref(o))
     if st != PSZ_SUCCESS:
         raise PszError(st, "psz_amd_region_plan")
     return o
@@ -355,6 +362,13 @@ class Resource:
         st = f(self._h, C.c_void_p(d_archive), nbytes, _origin3(origin), _len3(extent), C.c_void_p(d_out))
         if st != PSZ_SUCCESS:
             raise PszError(st, "psz_amd_decompress_region")
+
+    def set_region_mode(self, mode: int):
+        """REGION_MODE_WHOLE (default: archives off the fused path decode whole) or
+        REGION_MODE_COVER (only the covering slab of such an archive is decoded)."""
+        st = lib().psz_amd_set_region_mode(self._h, mode)
+        if st != PSZ_SUCCESS:
+            raise PszError(st, "psz_amd_set_region_mode")
 
     def last_region(self) -> psz_amd_region_info:
         """What the last region call did (the path taken after the device-side checks)."""

@@ -330,8 +330,21 @@ int psz_amd_assess_quality_region_double(psz_resource* m, const double* xbox, co
 
 int psz_amd_region_plan(const psz_header* h, psz_len origin, psz_len extent, psz_amd_region_info* out)
 {
+  return psz_amd_region_plan_mode(h, origin, extent, PSZ_AMD_REGION_MODE_WHOLE, out);
+}
+
+int psz_amd_region_plan_mode(const psz_header* h, psz_len origin, psz_len extent, int mode, psz_amd_region_info* out)
+{
   if (!h || !out) return PSZ_AMD_ERR_INVALID_ARG;
-  return cusz_amd::region_plan(h, origin, extent, out);
+  return cusz_amd::region_plan(h, origin, extent, mode, out);
+}
+
+int psz_amd_set_region_mode(psz_resource* m, int mode)
+{
+  Pipeline* p = P(m);
+  if (!p || (mode != PSZ_AMD_REGION_MODE_WHOLE && mode != PSZ_AMD_REGION_MODE_COVER)) return PSZ_AMD_ERR_INVALID_ARG;
+  p->region_mode = mode;
+  return PSZ_SUCCESS;
 }
 
 int psz_amd_decompress_region_float(psz_resource* m, uint8_t* in, size_t in_len, psz_len origin, psz_len extent,

@@ -69,6 +69,7 @@ struct PhfView {
   size_t bs_words;  // words from the bitstream's start to the archive's end (the range of the
                     // decoders' loads); 0 when entry[5] does not reach the bitstream
   size_t bits_words;  // the bitstream's own cells (to the outlier cells at entry[3]); 0 likewise
+                      // (a chunks() view: its chunks' share, see there)
   const uint8_t* revbook;
   const uint32_t* par_nbit;
   const uint32_t* par_entry;
@@ -90,6 +91,18 @@ struct PhfView {
     bs_words = total > bits_off ? (total - bits_off) / 4 : 0;
     const size_t cells_off = h->entry[PSZHEADER_SPFMT];
     bits_words = cells_off > bits_off ? (cells_off - bits_off) / 4 : 0;
+  }
+  // Chunks [c0, c1) as a view of their own (0 <= c0 <= c1 <= pardeg): the decoders then write chunk
+  // c0's codes at their output pointer.  The bitstream and its word counts stay, because
+  // par_entry counts cells from the bitstream's start.  bits_words, which only sizes the WAVE
+  // decoder's staging by the average chunk, becomes the range's share at the archive's average.
+  PhfView chunks(size_t c0, size_t c1) const
+  {
+    PhfView v = *this;
+    v.par_nbit += c0, v.par_entry += c0;
+    v.bits_words = pardeg > 0 ? bits_words / (size_t)pardeg * (c1 - c0) : 0;
+    v.pardeg = (int)(c1 - c0);
+    return v;
   }
 };
 

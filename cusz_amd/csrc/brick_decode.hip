@@ -1,6 +1,7 @@
 // cusz_amd/csrc/brick_decode.hip -- the fused brick decoders (overview: brick_device.hh): the chunk
 // loop decode_chunks4 and the kernels built on it -- k_brick3_decode, k_brick3_region (a box of the
-// field), k_brick1_decode, k_chunk_decode (codes only) -- with k_brick_cell_bounds and the launchers.
+// field), k_brick1_decode and, as its REGION instantiation, k_brick1_region (a range of a 1-D field),
+// k_chunk_decode (codes only) -- with k_brick_cell_bounds and the launchers.
 #include "brick_device.hh"
 
 namespace cusz_amd {
@@ -916,27 +917,62 @@ constexpr int kD1MaxWaves = (int)((160 * 1024 - sizeof(hfd::Tab4) - 512) / kD1Wa
 static_assert(kD1MaxWaves >= 4, "LDS");
 static_assert(64 * 144 <= 64 * kTP4 * 2, "store staging fits the code tile");
 
-template <typename T, bool ZZ>
+//
+// REGION (k_brick1_region): the same walk over the tiles [t0, t1) that cover the range [o, o + e)
+// of the field only, unit u of the launch taking tiles t0 + 64 u + lane, and `out` the compact
+// range.  Chunks wholly past the range are skipped; chunks of the first tile before it are decoded
+// and summed (the tile's carry needs them) and store nothing.  Every element is stored by a guarded
+// global store at its index in the range: no buffer resource or base reaching outside the range's
+// allocation is formed.  Non-ZigZag, ranked cells only (the caller has read the bounds pass's
+// verdict).  Waves [wpb, 8) of a workgroup only help build the tables; a wave takes one unit
+// (launch_brick1_region), units wave-major so that they spread over the CUs first.
+struct Region1 {
+  uint32_t t0, t1;  // covering tiles of 1024
+  size_t o, e;      // the range, in elements
+  uint32_t wpb;     // decoding waves per workgroup
+};
+
+struct NoRegion1 {};
+
+// k_brick1_decode<T, ZZ> (the field) and k_brick1_decode<T, false, true> = k_brick1_region (a range
+// of it): one body, the region's differences under `if constexpr (REGION)`.
+template <typename T, bool ZZ, bool REGION = false>
 __global__ void __launch_bounds__(64 * kDecWaves)
 k_brick1_decode(const uint32_t* __restrict__ bitstream, uint32_t bs_words, const uint8_t* __restrict__ revbook,
                 int bklen, const uint32_t* __restrict__ par_nbit, const uint32_t* __restrict__ par_entry, T* out,
-                size_t n, T ebx2, T r, uint32_t nchunks, uint32_t nunits, BrickOutliers ol)
+                size_t n, T ebx2, T r, uint32_t nchunks, uint32_t nunits, BrickOutliers ol,
+                std::conditional_t<REGION, Region1, NoRegion1> rg1)
 {
   __shared__ hfd::Tab4 tb;
   extern __shared__ __attribute__((aligned(16))) uint8_t dsm[];
   hfd::build_tab4(tb, revbook, bklen);
   const hfd::DecRegs4 rg = hfd::load_dec_regs4(tb);
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if constexpr (REGION)
+    if ((uint32_t)wid >= rg1.wpb) return;
   uint8_t* wbase = dsm + (size_t)wid * kD1WaveBytes;
   uint16_t* tile = reinterpret_cast<uint16_t*>(wbase + kD4Tile);
   uint32_t* cv = reinterpret_cast<uint32_t*>(wbase + kD1Cv) + lane * kCvPitch;  // this lane's values
-  const bool ranked = !ZZ && (ol.ncell == 0 || *ol.unsorted != ol.epoch);  // else: values in `out` (scatter)
+  // else: values in `out` (scatter); REGION: the caller has checked
+  const bool ranked = !ZZ && (REGION || ol.ncell == 0 || *ol.unsorted != ol.epoch);
   const uint32_t npf = ol.ncell < (1u << 28) ? kCellPf : 0u;  // prefetched ranks (32-bit buffer offsets)
   const DecWave4 dw{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(bitstream), 0, (int)(bs_words * 4u), (int)kBufRsrcW3),
                     reinterpret_cast<uint32_t*>(wbase) + lane, tile, (uint32_t)bklen, lane};
   const __amdgpu_buffer_rsrc_t rcells = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint32_t*>(ol.cells), 0, (int)min(ol.ncell * 8, (size_t)0x7FFFFFFF), (int)kBufRsrcW3);
-  const uint32_t nw = gridDim.x * (blockDim.x >> 6);
+  uint32_t nw_, u0_;  // REGION: units wave-major, so that they spread over the workgroups first
+  if constexpr (REGION) nw_ = gridDim.x * rg1.wpb, u0_ = (uint32_t)wid * gridDim.x + blockIdx.x;
+  else nw_ = gridDim.x * (blockDim.x >> 6), u0_ = blockIdx.x * (blockDim.x >> 6) + wid;
+  const uint32_t nw = nw_, u0 = u0_;
+  // chunk p of this lane's tile in unit u, and whether it is decoded
+  auto chunk_of = [&](uint32_t u, uint32_t p) {
+    if constexpr (REGION) return ((size_t)rg1.t0 + (size_t)u * 64u + (uint32_t)lane) * 4u + p;
+    else return ((size_t)u * 64u + (uint32_t)lane) * 4u + p;
+  };
+  auto wanted = [&](size_t c) {
+    if constexpr (REGION) return c / 4u < rg1.t1 && c < nchunks && c * 256u < rg1.o + rg1.e;
+    else return c < nchunks;
+  };
   BPROF(unsigned long long pc[16] = {}; unsigned long long tk = __builtin_readcyclecounter(), tp = tk;)
   // chunk size / offset and cell range of each phase's chunk, loaded during the previous phase's
   // last block (they land while it decodes)
@@ -945,26 +981,27 @@ k_brick1_decode(const uint32_t* __restrict__ bitstream, uint32_t bs_words, const
   };
   auto fetch = [&](uint32_t u, uint32_t p) {
     Next x{0, 0, 0, 0};
-    const size_t c = ((size_t)u * 64u + (uint32_t)lane) * 4u + p;
-    if (u < nunits && c < nchunks) {
+    const size_t c = chunk_of(u, p);
+    if (u < nunits && wanted(c)) {
       x.nbit = par_nbit[c], x.entry = par_entry[c];
       if (ranked && ol.ncell) x.cb = ol.bstart[c], x.ce = ol.bstart[c + 1];
     }
     return x;
   };
-  Next nxt = fetch(blockIdx.x * (blockDim.x >> 6) + wid, 0);
-  for (uint32_t u = blockIdx.x * (blockDim.x >> 6) + wid; u < nunits; u += nw) {
+  Next nxt = fetch(u0, 0);
+  for (uint32_t u = u0; u < nunits; u += nw) {
     T carry = T(0);  // serial sum of this tile's segment totals (exclusive)
     T fh[16];        // raw thread totals of the current segment's first half
     const size_t ubase = (size_t)u * 65536u;
     const bool full = ubase + 65536u <= n;  // every element of the unit is in the field (uniform)
     // unit-relative stores: 32-bit offsets; past the field's end they are dropped
+    // (REGION: an empty resource, never used; the stores are element stores below)
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        out + ubase, 0, (int)(min((size_t)65536u, n - ubase) * sizeof(T)), (int)kBufRsrcW3);
+        out + (REGION ? 0 : ubase), 0, REGION ? 0 : (int)(min((size_t)65536u, n - ubase) * sizeof(T)), (int)kBufRsrcW3);
     for (uint32_t p = 0; p < 4; p++) {
       BPROF(pc[0]++; tp = __builtin_readcyclecounter();)
-      const size_t c = ((size_t)u * 64u + (uint32_t)lane) * 4u + p;
-      const bool live = c < nchunks;
+      const size_t c = chunk_of(u, p);
+      const bool live = wanted(c);
       const Next me = nxt;
       const uint32_t nbit = live ? me.nbit : 0u;
       const uint32_t vbase = (live ? me.entry : 0u) * 4u;
@@ -1156,7 +1193,15 @@ k_brick1_decode(const uint32_t* __restrict__ bitstream, uint32_t bs_words, const
 #pragma unroll
               for (int k = 0; k < 4; k++) o[k] = (v[4 * t + k] + carry) * ebx2;
             }
-            if (full) {
+            if constexpr (REGION) {
+              const size_t g0 = c * 256u + (uint32_t)blk * kBlk + 4u * (uint32_t)t;
+#pragma unroll
+              for (int k = 0; k < 4; k++) {
+                const size_t g = g0 + (uint32_t)k;
+                if (live && g >= rg1.o && g - rg1.o < rg1.e) out[g - rg1.o] = o[k];
+              }
+            }
+            else if (full) {
               // through the tile's space (the codes are in registers): RE elements of every row
               // per round (128 B), then each store instruction writes whole 128-B pieces of
               // 64 / (RE / 4) rows instead of 16-B pieces of 64 rows
@@ -1292,10 +1337,10 @@ int launch_brick_decode(const BrickLaunch& L, const PhfView& v, T* out, double e
     const size_t lds1 = (size_t)wpb * kD1WaveBytes;
     if (zz)
       k_brick1_decode<T, true><<<grid, 64 * wpb, lds1, st>>>(v.bitstream, (uint32_t)v.bs_words, v.revbook, v.bklen, v.par_nbit,
-                                                             v.par_entry, out, g.n, ebx2, r, g.nchunks, nunits, ol);
+                                                             v.par_entry, out, g.n, ebx2, r, g.nchunks, nunits, ol, NoRegion1{});
     else
       k_brick1_decode<T, false><<<grid, 64 * wpb, lds1, st>>>(v.bitstream, (uint32_t)v.bs_words, v.revbook, v.bklen, v.par_nbit,
-                                                              v.par_entry, out, g.n, ebx2, r, g.nchunks, nunits, ol);
+                                                              v.par_entry, out, g.n, ebx2, r, g.nchunks, nunits, ol, NoRegion1{});
     return (int)hipGetLastError();
   }
   // buffer stores address a brick block with 32-bit offsets from its first element
@@ -1364,6 +1409,28 @@ int launch_brick_region(const BrickLaunch& L, const PhfView& v, T* out_box, doub
   return (int)hipGetLastError();
 }
 
+template <typename T>
+int launch_brick1_region(const BrickLaunch& L, const PhfView& v, T* out_box, double eb, int radius,
+                         const BrickOutliers& ol, size_t o, size_t e, hipStream_t st)
+{
+  const BrickGeom& g = L.g;
+  if (!g.ok || g.ndim != 1 || g.W != 256 || v.bs_words >= (1ull << 30) || v.bklen < 1 || v.bklen > kMaxBklen || !e ||
+      o >= g.n || e > g.n - o || (uint32_t)v.pardeg != g.nchunks || L.ncu < 1)
+    return (int)hipErrorInvalidValue;
+  const Region1Tiles t = region_tiles1(o, e);
+  const uint32_t nunits = (uint32_t)((t.t1 - t.t0 + 63) / 64);
+  // one unit per wave; one wave per workgroup while the units fit the CUs (a small range is bound
+  // by one tile's serial walk), then more decoding waves per workgroup
+  const uint32_t wmax = (uint32_t)std::min<int>(kDecWaves, kD1MaxWaves);
+  const uint32_t wpb = std::max(1u, std::min(wmax, (nunits + (uint32_t)L.ncu - 1) / (uint32_t)L.ncu));
+  const uint32_t grid = (nunits + wpb - 1) / wpb;
+  const Region1 rg1{(uint32_t)t.t0, (uint32_t)t.t1, o, e, wpb};
+  k_brick1_decode<T, false, true><<<grid, 64 * kDecWaves, (size_t)wpb * kD1WaveBytes, st>>>(
+      v.bitstream, (uint32_t)v.bs_words, v.revbook, v.bklen, v.par_nbit, v.par_entry, out_box, g.n, (T)(eb * 2), (T)radius,
+      g.nchunks, nunits, ol, rg1);
+  return (int)hipGetLastError();
+}
+
 int launch_chunk_decode(uint32_t ncu, const PhfView& v, uint16_t* codes, size_t n, hipStream_t st)
 {
   const uint32_t nchunks = (uint32_t)v.pardeg, sublen = (uint32_t)v.sublen;
@@ -1399,7 +1466,9 @@ extern "C" int psz_amd_debug_brick_profile(unsigned long long* host, int reset)
   template int launch_brick_decode<T>(const BrickLaunch&, const PhfView&, T*, double, int, bool, const BrickOutliers&, \
                                       hipStream_t);                                                                \
   template int launch_brick_region<T>(const BrickLaunch&, const PhfView&, T*, double, int, const BrickOutliers&,   \
-                                      const uint32_t(&)[3], const uint32_t(&)[3], hipStream_t);
+                                      const uint32_t(&)[3], const uint32_t(&)[3], hipStream_t);             \
+  template int launch_brick1_region<T>(const BrickLaunch&, const PhfView&, T*, double, int, const BrickOutliers&, size_t, \
+                                       size_t, hipStream_t);
 INST(float)
 INST(double)
 #undef INST

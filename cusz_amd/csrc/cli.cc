@@ -57,7 +57,8 @@ static void usage()
       "usage: cusz -z -t f32|f64 -m abs|rel|r2r -e EB -l X[xY[xZ]] -i FILE [-p lrz|lrz-zz] [-R time,cr]\n"
       "               [--codec huffman|fzgcodec]  (fzgcodec: no codebook, lrz / lrz-zz only; -x reads it from the archive)\n"
       "       cusz -x -i FILE.cusza [--origin FILE] [-R time] [-S write2disk]\n"
-      "               [--region X0[,Y0[,Z0]]:EX[,EY[,EZ]]]  (decode only this box, in elements)\n");
+      "               [--region X0[,Y0[,Z0]]:EX[,EY[,EZ]]]  (decode only this box, in elements)\n"
+      "               [--region-mode whole|cover]  (cover: decode only the chunks that cover the box)\n");
 }
 
 // "x0[,y0[,z0]]:ex[,ey[,ez]]" -> origin (missing axes 0) and extent (missing axes 1)
@@ -161,13 +162,28 @@ int main(int argc, char** argv)
   // --region is this build's own flag: taken out before the reference's parser sees argv
   bool region = false;
   psz_len r_origin{0, 0, 0}, r_extent{1, 1, 1};
+  // --region-mode likewise.  Its default is `whole`: an FZG archive's --region summary is expected
+  // to say `fallback`, which `cover` would turn into `slab`.
+  int region_mode = PSZ_AMD_REGION_MODE_WHOLE;
+  bool region_mode_set = false;
   for (int i = 1; i < argc; i++) {
-    if (std::strcmp(argv[i], "--region")) continue;
-    if (i + 1 >= argc || !parse_region(argv[i + 1], &r_origin, &r_extent)) {
+    const bool is_mode = !std::strcmp(argv[i], "--region-mode");
+    if (std::strcmp(argv[i], "--region") && !is_mode) continue;
+    if (is_mode) {
+      const char* v = i + 1 < argc ? argv[i + 1] : "";
+      if (std::strcmp(v, "whole") && std::strcmp(v, "cover")) {
+        std::fprintf(stderr, "[cusz] --region-mode needs whole or cover\n");
+        return usage(), 1;
+      }
+      region_mode = std::strcmp(v, "cover") ? PSZ_AMD_REGION_MODE_WHOLE : PSZ_AMD_REGION_MODE_COVER;
+      region_mode_set = true;
+    }
+    else if (i + 1 >= argc || !parse_region(argv[i + 1], &r_origin, &r_extent)) {
       std::fprintf(stderr, "[cusz] --region needs X0[,Y0[,Z0]]:EX[,EY[,EZ]]\n");
       return usage(), 1;
     }
-    region = true;
+    else
+      region = true;
     for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
     argc -= 2;
     i--;
@@ -185,6 +201,10 @@ int main(int argc, char** argv)
 
   if (region && !ctx->cli->task_reconstruct) {
     std::fprintf(stderr, "[cusz] --region goes with -x\n");
+    return usage(), 1;
+  }
+  if (region_mode_set && !region) {
+    std::fprintf(stderr, "[cusz] --region-mode goes with --region\n");
     return usage(), 1;
   }
   if (ctx->cli->task_construct) {
@@ -258,6 +278,7 @@ int main(int argc, char** argv)
     if (!m) return std::fprintf(stderr, "[cusz] cannot create resource manager\n"), 1;
     if (region) {  // only the box is decoded and written
       const size_t nb = r_extent.x * r_extent.y * r_extent.z;
+      psz_amd_set_region_mode(m, region_mode);
       auto t0 = clk::now();
       int s = h.dtype == F4 ? psz_amd_decompress_region_float(m, d_arch, arch.size(), r_origin, r_extent, (float*)d_out)
                             : psz_amd_decompress_region_double(m, d_arch, arch.size(), r_origin, r_extent, (double*)d_out);
@@ -271,9 +292,12 @@ int main(int argc, char** argv)
       std::string base(ctx->cli->file_input);
       if (base.size() > 6 && base.substr(base.size() - 6) == ".cusza") base = base.substr(0, base.size() - 6);
       if (!ctx->cli->skip_tofile && !write_file(base + ".cuszx", out.data(), out.size())) return 1;
-      std::printf("decompressed region %zu,%zu,%zu:%zux%zux%zu of %s -> %s.cuszx (%zu bytes, %s, %zu bricks)\n",
+      // what was decoded: bricks on the fused path, else chunks (FZG: blocks)
+      std::printf("decompressed region %zu,%zu,%zu:%zux%zux%zu of %s -> %s.cuszx (%zu bytes, %s, %zu %s)\n",
                   r_origin.x, r_origin.y, r_origin.z, r_extent.x, r_extent.y, r_extent.z, ctx->cli->file_input,
-                  base.c_str(), nb * es, ri.path == PSZ_AMD_REGION_FUSED ? "fused" : "fallback", ri.bricks);
+                  base.c_str(), nb * es,
+                  ri.path == PSZ_AMD_REGION_FUSED ? "fused" : ri.path == PSZ_AMD_REGION_SLAB ? "slab" : "fallback",
+                  ri.bricks ? ri.bricks : ri.chunks, ri.bricks ? "bricks" : "chunks");
       if (ctx->cli->report_time) std::printf("time: region decompress %.3f ms (wall)\n", wall);
       if (ctx->cli->file_compare[0] && report_quality(m, h, ctx->cli->file_compare, d_out, true, r_origin, r_extent)) return 1;
       psz_release_resource(m);

@@ -3,6 +3,7 @@
 
 #include "archive_layout.hh"
 #include "common.hh"
+#include "region_cover.hh"
 
 namespace cusz_amd {
 
@@ -379,10 +380,21 @@ RegionBox region_box(uint32_t ox, uint32_t oy, uint32_t oz, uint32_t ex, uint32_
 template <typename T>
 int launch_brick_region(const BrickLaunch& L, const PhfView& v, T* out_box, double eb, int radius,
                         const BrickOutliers& ol, const uint32_t (&o)[3], const uint32_t (&e)[3], hipStream_t st);
+// Region decode, 1-D brick fields (Lorenzo, chunk length 256, ranked cells, ol.bstart over chunks:
+// launch_x1d_bounds with ushift 8): the range of e elements at o, decoded from its covering tiles
+// of 1024 only (region_cover.hh region_tiles1) into out_box.
+template <typename T>
+int launch_brick1_region(const BrickLaunch& L, const PhfView& v, T* out_box, double eb, int radius,
+                         const BrickOutliers& ol, size_t o, size_t e, hipStream_t st);
 // out_box[(z ey + y) ex + x] = field[((oz + z) ly + oy + y) lx + ox + x] (the region fallback)
 template <typename T>
 int launch_crop_box(const T* field, size_t lx, size_t ly, const size_t (&o)[3], const size_t (&e)[3], T* out_box,
                     hipStream_t st);
+
+// the outlier cells with lo <= idx < hi into slab[idx - lo] (the region decode's SLAB path); the
+// cells in any order
+template <typename T>
+int launch_scatter_range(const uint32_t* cells, size_t nnz, T* slab, size_t lo, size_t hi, hipStream_t st);
 
 // min / max (Rel mode, extrema.cuhip.inl:86-208), writes {min, max} as doubles
 template <typename T>

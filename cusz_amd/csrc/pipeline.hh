@@ -40,6 +40,7 @@
 #include "cusz_rev1.h"
 #include "kernels.hh"
 #include "quality_reduce.hh"
+#include "region_cover.hh"
 
 #pragma GCC visibility push(hidden)  // internal to the library: the exports are the C API's
 namespace cusz_amd {
@@ -54,7 +55,7 @@ inline bool box_inside(psz_len l, psz_len o, psz_len e)
          o.z < l.z && e.z <= l.z - o.z;
 }
 
-int region_plan(const psz_header* h, psz_len o, psz_len e, psz_amd_region_info* out);  // pipeline_decode.cc
+int region_plan(const psz_header* h, psz_len o, psz_len e, int mode, psz_amd_region_info* out);  // pipeline_decode.cc
 void tune_chunking(size_t n, int device, int* sublen, int* pardeg);                    // pipeline.cc
 
 // An allocation that frees itself: device memory, or (Pinned) host memory that is mapped and
@@ -74,6 +75,21 @@ struct DevBuf {
   }
   void free() { if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p)), p = nullptr; }
   operator T*() const { return p; }
+};
+
+// device bytes that grow on demand and never shrink (what they held is not kept)
+struct GrowBuf {
+  DevBuf<uint8_t> buf;
+  size_t bytes = 0;
+  hipError_t grow(size_t need)
+  {
+    if (need <= bytes) return hipSuccess;
+    bytes = 0;
+    const hipError_t e = buf.alloc(need);
+    if (e == hipSuccess) bytes = need;
+    return e;
+  }
+  uint8_t* p() const { return buf.p; }
 };
 
 struct Event {  // likewise
@@ -186,6 +202,9 @@ struct Pipeline {
   uint32_t cell_epoch = 0;        // tags the unsorted flag of the current decompress (never 0)
   uint32_t next_cell_epoch() { return cell_epoch = cell_epoch + 1 ? cell_epoch + 1 : 1; }
   DevBuf<uint8_t> d_region_field;  // region fallback: the whole field (allocated on first use)
+  GrowBuf d_region_slab;           // region SLAB path: the covering slab.  It only grows: the largest slab a
+                                   // manager has decoded stays allocated until the manager is released
+  int region_mode = PSZ_AMD_REGION_MODE_WHOLE;  // PSZ_AMD_REGION_MODE_*
   DevBuf<QrPart> d_quality;        // quality assessment: workgroup records + the result (allocated on first use)
   psz_amd_region_info last_region{};
   bool has_last_region = false;
@@ -341,6 +360,8 @@ struct Pipeline {
   int decompress(const psz_header* h, const uint8_t* in, T* out);
   template <typename T>
   int decompress_region(const psz_header* h, const uint8_t* in, psz_len o, psz_len e, T* out);
+  template <typename T>
+  int decompress_slab(const psz_header* h, const uint8_t* in, psz_len o, psz_len e, T* out, psz_amd_region_info* info);
   template <typename T>
   int decompress_spline(const psz_header* h, const uint8_t* in, T* out);
 };

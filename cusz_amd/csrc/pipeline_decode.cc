@@ -7,10 +7,24 @@
 
 namespace cusz_amd {
 
+// An archive whose covering slab decodes on its own (the SLAB path): Lorenzo of either kind,
+// codes in index order behind Huffman chunks or FZG blocks.
+static bool slab_archive(const psz_header* h)
+{
+  const psz_predictor p = h->pipeline.predictor;
+  if (p != Lorenzo && p != LorenzoZigZag) return false;
+  if (h->pipeline.codec1 == FZCodec) return h->vle_pardeg > 0;
+  return h->pipeline.codec1 == Huffman && h->vle_sublen > 0 && h->vle_pardeg > 0;
+}
+
 // What a region decode of an archive with header h touches (psz_amd_region_plan): the header's
 // share of Pipeline::decompress_region's path choice, and the covering bricks.
-int region_plan(const psz_header* h, psz_len o, psz_len e, psz_amd_region_info* out)
+// mode (PSZ_AMD_REGION_MODE_*): under COVER every Lorenzo archive that is no fused candidate
+// takes SLAB, the covering chunks (blocks) of region_cover.hh; WHOLE is the verdict as it was
+// before the mode existed.
+int region_plan(const psz_header* h, psz_len o, psz_len e, int mode, psz_amd_region_info* out)
 {
+  if (mode != PSZ_AMD_REGION_MODE_WHOLE && mode != PSZ_AMD_REGION_MODE_COVER) return PSZ_AMD_ERR_INVALID_ARG;
   const psz_len l = h->len;
   if (!box_inside(l, o, e)) return PSZ_AMD_ERR_INVALID_ARG;
   psz_amd_region_info r{};
@@ -29,6 +43,24 @@ int region_plan(const psz_header* h, psz_len o, psz_len e, psz_amd_region_info* 
     r.brick_n = psz_len{b.bnx, b.bny, b.bnz};
     r.bricks = (size_t)b.bnx * b.bny * b.bnz;
     r.chunks = r.bricks * 64;
+  }
+  else if (mode == PSZ_AMD_REGION_MODE_COVER && g.ok && nd == 1 && g.W == 256 && h->pipeline.predictor == Lorenzo &&
+           h->pipeline.codec1 == Huffman && h->vle_sublen == 256 && h->vle_pardeg > 0 &&
+           (uint32_t)h->vle_pardeg == g.nchunks && 2 * (int)h->rc.radius <= kMaxBklen) {
+    // the fused 1-D path (k_brick1_region): the covering tiles of 1024 stand in the brick fields
+    const Region1Tiles t = region_tiles1(o.x, e.x);
+    r.path = PSZ_AMD_REGION_FUSED;
+    r.brick_lo = psz_len{t.t0, 0, 0};
+    r.brick_n = psz_len{t.t1 - t.t0, 1, 1};
+    r.bricks = t.t1 - t.t0;
+    r.chunks = t.chunks(g.nchunks);
+  }
+  else if (mode == PSZ_AMD_REGION_MODE_COVER && slab_archive(h)) {
+    const bool fzg = h->pipeline.codec1 == FZCodec;
+    const RegionCover c = region_cover(nd, l.x, l.y, l.z, slow_axis(nd, o), slow_axis(nd, e),
+                                       fzg ? (size_t)kFzgBlock : (size_t)h->vle_sublen, (size_t)h->vle_pardeg);
+    r.path = PSZ_AMD_REGION_SLAB;
+    r.chunks = c.chunks();
   }
   else {
     r.path = PSZ_AMD_REGION_FALLBACK;
@@ -138,7 +170,9 @@ int Pipeline::decompress(const psz_header* h, const uint8_t* in, T* out)
 // the covering bricks are decoded (brick_decode.hip k_brick3_region), which needs the fused 3-D
 // decoder's conditions and ranked outlier cells -- the bounds pass's verdict is the one word
 // read back here, before the decode is queued.  FALLBACK: the whole field into a scratch
-// field, then the box copied out.
+// field, then the box copied out.  COVER only: FUSED also for 1-D brick archives (k_brick1_region
+// over the covering tiles of 1024, the same read-back after launch_x1d_bounds over chunks), and
+// SLAB: decompress_slab below.
 template <typename T>
 int Pipeline::decompress_region(const psz_header* h, const uint8_t* in, psz_len o, psz_len e, T* out)
 {
@@ -146,25 +180,40 @@ int Pipeline::decompress_region(const psz_header* h, const uint8_t* in, psz_len 
   if (!known_predictor(h->pipeline.predictor)) return PSZ_ABORT_NO_SUCH_PREDICTOR;
   if (h->len.x != len.x || h->len.y != len.y || h->len.z != len.z) return PSZ_ABORT_UNSUPPORTED_DIMENSION;
   psz_amd_region_info info;
-  if (const int s = region_plan(h, o, e, &info)) return s;
+  if (const int s = region_plan(h, o, e, region_mode, &info)) return s;
   bool fused = info.path == PSZ_AMD_REGION_FUSED && bl.g.ok && decoder == 0;
+  // COVER: a fused candidate that the checks below refuse, and every SLAB verdict, decode the
+  // covering slab.  The decoders store 16 bytes at a time from the start of their output, so a
+  // chunk length that is no multiple of 8 codes (none this compressor writes) keeps the fallback.
+  const bool slab = region_mode == PSZ_AMD_REGION_MODE_COVER && info.path != PSZ_AMD_REGION_FALLBACK &&
+                    (h->pipeline.codec1 == FZCodec || h->vle_sublen % 8 == 0);
   BrickOutliers bo;
   if (fused && h->splen) {
     const uint32_t* cells = reinterpret_cast<const uint32_t*>(in + h->entry[PSZHEADER_SPFMT]);
-    const uint32_t nb = bl.g.nbricks;
-    CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_cell_bounds(bl, cells, h->splen, d_x1d, d_x1d + nb + 1,
-                                                            next_cell_epoch(), stream));
+    // cells per brick (3-D) or per chunk (1-D), as the full decompress ranks them
+    const uint32_t nb = ndim == 1 ? bl.g.nchunks : bl.g.nbricks;
+    if (ndim == 1)
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_x1d_bounds(cells, h->splen, n, nb, d_x1d, d_x1d + nb + 1, next_cell_epoch(),
+                                                       stream, 8));
+    else
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_cell_bounds(bl, cells, h->splen, d_x1d, d_x1d + nb + 1,
+                                                              next_cell_epoch(), stream));
     uint32_t word = 0;
     CUSZ_AMD_HIP_CHECK(hipMemcpyAsync(&word, d_x1d + nb + 1, 4, hipMemcpyDeviceToHost, stream));
     CUSZ_AMD_HIP_CHECK(hipStreamSynchronize(stream));
     fused = word != cell_epoch;
     bo = BrickOutliers{cells, (size_t)h->splen, d_x1d, d_x1d + nb + 1, cell_epoch};
   }
-  if (fused) {
+  if (fused && ndim == 1)  // (COVER only: region_plan)
+    CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick1_region<T>(bl, PhfView(h, in), out, h->rc.eb, h->rc.radius, bo, o.x, e.x, stream));
+  else if (fused) {
     // (vle_pardeg == bl.g.nchunks: region_plan)
     const uint32_t o3[3] = {(uint32_t)o.x, (uint32_t)o.y, (uint32_t)o.z}, e3[3] = {(uint32_t)e.x, (uint32_t)e.y, (uint32_t)e.z};
     CUSZ_AMD_HIP_CHECK(
         (hipError_t)launch_brick_region<T>(bl, PhfView(h, in), out, h->rc.eb, h->rc.radius, bo, o3, e3, stream));
+  }
+  else if (slab) {
+    if (const int s = decompress_slab<T>(h, in, o, e, out, &info)) return s;
   }
   else {
     if (!d_region_field) CUSZ_AMD_HIP_CHECK(d_region_field.alloc(n * sizeof(T)));
@@ -178,6 +227,66 @@ int Pipeline::decompress_region(const psz_header* h, const uint8_t* in, psz_len 
   }
   last_region = info;
   has_last_region = true;
+  return PSZ_SUCCESS;
+}
+
+// SLAB: the tile-aligned slab [a, b) of the slow axis that covers the box (region_cover.hh), and
+// nothing else.  The chunks (blocks) that hold the slab's codes decode to their natural positions
+// in d_codes; the outlier cells of the slab go into a slab-sized scratch, in whatever order the
+// archive holds them; the slab reconstructs as a field of its own extents (prediction restarts at
+// every tile: DESIGN.md §4, "Region decode"), and the box is cropped out of it.  Lorenzo of
+// either kind, Huffman in any layout or FZG, any decoder.  No host wait beyond check_fzg's.
+template <typename T>
+int Pipeline::decompress_slab(const psz_header* h, const uint8_t* in, psz_len o, psz_len e, T* out, psz_amd_region_info* info)
+{
+  const bool fzg = h->pipeline.codec1 == FZCodec, zz = h->pipeline.predictor == LorenzoZigZag;
+  FzgHeader fh{};
+  if (fzg) {
+    if (const int s = check_fzg(h, in, &fh)) return s;
+  }
+  const size_t unit = fzg ? (size_t)kFzgBlock : (size_t)h->vle_sublen;
+  // (FZG: the segment's own block count, which check_fzg has matched against the field; the full
+  // decode does not look at vle_pardeg either)
+  const RegionCover c = region_cover(ndim, len.x, len.y, len.z, slow_axis(ndim, o), slow_axis(ndim, e), unit,
+                                     fzg ? FzgLayout(n).blocks : (size_t)h->vle_pardeg);
+  // 1. codes [c0 unit, min(n, c1 unit)) at their places in d_codes
+  const size_t code0 = c.c0 * unit, code1 = std::min(n, c.c1 * unit);
+  if (code1 > code0) {
+    if (fzg) {
+      const FzgView v(h, n);
+      const uint8_t* seg = in + v.seg_off;
+      const FzgDecodeArgs da{reinterpret_cast<const uint64_t*>(seg + v.l.flags_rel) + (size_t)kFzgBlockUnits * c.c0,
+                             reinterpret_cast<const uint32_t*>(seg + v.l.off_rel) + c.c0,
+                             reinterpret_cast<const uint64_t*>(seg + v.l.payload_rel), fh.total_words, code1 - code0,
+                             (int)h->rc.radius, fh.transform, d_codes + code0};
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_fzg_decode(da, stream));
+    }
+    else
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_hf_decode(PhfView(h, in).chunks(c.c0, c.c1), code1 - code0, d_codes + code0,
+                                                      dec_lut(), decoder, ncu, stream));
+  }
+  // 2. the slab's scratch: (b - a) P elements
+  const size_t lo = c.a * c.P, hi = c.b * c.P, bytes = (hi - lo) * sizeof(T);
+  CUSZ_AMD_HIP_CHECK(d_region_slab.grow(bytes));
+  T* slab = reinterpret_cast<T*>(d_region_slab.p());
+  if (zz) CUSZ_AMD_HIP_CHECK(hipMemsetAsync(slab, 0, bytes, stream));
+  // 3. its outlier cells
+  CUSZ_AMD_HIP_CHECK((hipError_t)launch_scatter_range<T>(reinterpret_cast<const uint32_t*>(in + h->entry[PSZHEADER_SPFMT]),
+                                                         h->splen, slab, lo, hi, stream));
+  // 4. reconstruct it as a field of (b - a) steps of the slow axis (the field's own dimension count,
+  //    also when one step is left); codes + a P is aligned as the field's rows and planes are
+  const size_t sl = c.b - c.a;
+  const size_t sx = ndim == 1 ? sl : len.x, sy = ndim == 2 ? sl : len.y, sz = ndim == 3 ? sl : len.z;
+  CUSZ_AMD_HIP_CHECK((hipError_t)launch_lorenzo_x<T>(d_codes + lo, slab, sx, sy, sz, h->rc.eb, h->rc.radius, zz,
+                                                     lorenzo_geom(ndim, sx, sy, sz, elem_bytes), stream, nullptr));
+  // 5. the box out of the slab
+  size_t o3[3] = {o.x, o.y, o.z};
+  o3[ndim - 1] -= c.a;
+  const size_t e3[3] = {e.x, e.y, e.z};
+  CUSZ_AMD_HIP_CHECK((hipError_t)launch_crop_box<T>(slab, sx, sy, o3, e3, out, stream));
+  const size_t elems = info->elems;
+  *info = psz_amd_region_info{};
+  info->path = PSZ_AMD_REGION_SLAB, info->elems = elems, info->chunks = c.chunks();
   return PSZ_SUCCESS;
 }
 

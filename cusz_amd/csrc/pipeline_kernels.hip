@@ -1,6 +1,7 @@
 // cusz_amd/csrc/pipeline_kernels.hip -- small device-side glue of the compress pipeline:
 // archive finalisation (segment sizes, outlier compaction, headers) and the Rel-mode
-// extrema probe.  Everything stays on the device; the host reads back one header at the end.
+// extrema probe; and of the region decode: the box cropped out of a field or a slab, the outlier
+// cells of a slab.  Everything stays on the device; the host reads back one header at the end.
 //
 // Reference counterparts: compress wrap-up psz/src/compressor.inl:398-418 (D2D concat),
 // phf header/offsets codec/hf/src/hf_buf.cc:191-211, GPU_extrema
@@ -311,7 +312,32 @@ __global__ void __launch_bounds__(256) k_crop_box(const T* __restrict__ field, s
   }
 }
 
+// The outlier cells of a slab of the field (the region decode's SLAB path): cell {f32 value, u32
+// idx} goes to slab[idx - lo] when lo <= idx < hi, converted as k_scatter (lorenzo.hip) converts
+// it.  One pass over all cells, in whatever order the archive holds them; 64-bit bounds.
+template <typename T>
+__global__ void __launch_bounds__(256) k_scatter_range(const uint32_t* __restrict__ cells, size_t nnz, T* __restrict__ slab,
+                                                       size_t lo, size_t hi)
+{
+  for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nnz; i += (size_t)gridDim.x * 256) {
+    const uint32_t vb = cells[2 * i];
+    const size_t idx = cells[2 * i + 1];
+    if (idx >= lo && idx < hi) slab[idx - lo] = (T)__builtin_bit_cast(float, vb);
+  }
+}
+
 }  // namespace
+
+template <typename T>
+int launch_scatter_range(const uint32_t* cells, size_t nnz, T* slab, size_t lo, size_t hi, hipStream_t st)
+{
+  if (nnz == 0 || hi <= lo) return (int)hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<size_t>((nnz + 255) / 256, 4096);
+  k_scatter_range<T><<<grid, 256, 0, st>>>(cells, nnz, slab, lo, hi);
+  return (int)hipGetLastError();
+}
+template int launch_scatter_range<float>(const uint32_t*, size_t, float*, size_t, size_t, hipStream_t);
+template int launch_scatter_range<double>(const uint32_t*, size_t, double*, size_t, size_t, hipStream_t);
 
 template <typename T>
 int launch_crop_box(const T* field, size_t lx, size_t ly, const size_t (&o)[3], const size_t (&e)[3], T* out_box,

@@ -164,7 +164,8 @@ int psz_amd_set_codebook(psz_resource* m, int mode);
  * psz_amd_internals.layout says so).  psz_amd_compress_scan_* still exports the histogram; of the
  * histogram passed to psz_amd_compress_finish only the overflow word counts.  Stage times:
  * PSZ_AMD_T_BOOK is 0, PSZ_AMD_T_ENCODE / _DECODE are the FZG kernels.  Region decode takes
- * PSZ_AMD_REGION_FALLBACK (psz_amd_region_plan says so).  psz_amd_merge_archives returns
+ * PSZ_AMD_REGION_FALLBACK (psz_amd_region_plan says so), or PSZ_AMD_REGION_SLAB over the covering
+ * blocks in PSZ_AMD_REGION_MODE_COVER.  psz_amd_merge_archives returns
  * PSZ_ABORT_NO_SUCH_CODEC for FZG parts. */
 
 /* ---- sharded compress (multi-GPU; the reference has no multi-GPU path) ----
@@ -221,25 +222,56 @@ int psz_amd_merge_archives(const uint8_t* const* parts, const size_t* part_bytes
  *    another order, a forced LANE / WAVE decoder): the whole field is decompressed into a scratch
  *    field the manager allocates on first use, and the box copied out.  Correct everywhere, not
  *    fast.
+ *  FUSED, 1-D (only in PSZ_AMD_REGION_MODE_COVER, below): 1-D brick-layout archives (Lorenzo,
+ *    Huffman, chunk length 256, one chunk per 256 elements, 2 radius <= 1024), default decoder,
+ *    cells in index order: only the tiles of 1024 elements that cover the range are decoded and
+ *    reconstructed in one kernel, and only the range is stored.  Here the brick fields count
+ *    TILES OF 1024 ELEMENTS: brick_lo = {t0, 0, 0}, brick_n = {t1 - t0, 1, 1}, bricks = t1 - t0
+ *    with t0 = origin.x / 1024 and t1 = ceil((origin.x + extent.x) / 1024); chunks = min(4 t1,
+ *    the archive's chunks) - 4 t0.
+ *  SLAB (only in PSZ_AMD_REGION_MODE_COVER, below): every Lorenzo / LorenzoZigZag archive, Huffman
+ *    or FZG, that is not FUSED.  Lorenzo prediction restarts at every tile, so only the slab of
+ *    whole tiles along the slowest axis that covers the box is decoded: [a, b) with a = floor(o /
+ *    T) T and b = min(len, ceil((o + e) / T) T), where T is 8 planes (3-D), 32 rows (2-D) or 1024
+ *    elements (1-D) and o, e the box's origin and extent on that axis.  The Huffman chunks (FZG:
+ *    the blocks of 4096) that hold the slab's codes are decoded, the slab's outlier cells
+ *    scattered (in any order), the slab reconstructed in a scratch of its own size and the box
+ *    copied out: time and memory follow the slab, not the field.
  * The work is queued on the manager's stream.  When the archive has outlier cells, a FUSED
  * candidate waits once for a 4-byte read-back (are the cells in brick order?) before its decode
  * is queued; no other host synchronisation.  Like psz_decompress_*, a region call invalidates a
  * pending psz_amd_compress_scan_*. */
 #define PSZ_AMD_REGION_FUSED 0
 #define PSZ_AMD_REGION_FALLBACK 1
+#define PSZ_AMD_REGION_SLAB 2
 typedef struct psz_amd_region_info {
-  int path;                  /* PSZ_AMD_REGION_FUSED or PSZ_AMD_REGION_FALLBACK               */
+  int path;                  /* PSZ_AMD_REGION_FUSED, _FALLBACK or _SLAB                      */
   psz_len brick_lo, brick_n; /* covering brick box: first brick, bricks per axis (FUSED), else zeros */
-  size_t bricks;             /* bricks decoded (FALLBACK: 0, the whole archive is decoded)    */
-  size_t chunks;             /* Huffman chunks decoded (FUSED: 64 per brick; FALLBACK: all)   */
+  size_t bricks;             /* bricks decoded (1-D FUSED: tiles of 1024; FALLBACK, SLAB: 0)  */
+  size_t chunks;             /* Huffman chunks decoded (FUSED: 64 per brick; FALLBACK: all;
+                              * SLAB: the chunks, or FZG blocks, that cover the slab)         */
   size_t elems;              /* extent.x * extent.y * extent.z                                */
 } psz_amd_region_info;
 
+/* How a manager decodes a region of an archive that is no FUSED candidate.
+ *  WHOLE (the default): FALLBACK, exactly as before the mode existed.
+ *  COVER: FUSED for 1-D brick-layout archives, SLAB for every other Lorenzo archive; a FUSED
+ *    candidate (1-D or 3-D) that the device-side checks refuse
+ *    (a forced decoder, cells in another order) takes SLAB too.  Spline and unknown codecs keep
+ *    FALLBACK, as does an archive whose chunk length is no multiple of 8 (none this compressor
+ *    writes).  The bits of the box are the same in either mode.
+ * Other values: PSZ_AMD_ERR_INVALID_ARG, the mode stays. */
+#define PSZ_AMD_REGION_MODE_WHOLE 0
+#define PSZ_AMD_REGION_MODE_COVER 1
+int psz_amd_set_region_mode(psz_resource* m, int mode);
+
 /* Host only, no GPU: validates the box against the header's field and says what a region decode
  * of such an archive touches.  The path is the header's verdict; the device-side checks (the
- * manager's decoder knob, the cells' order) can still turn FUSED into FALLBACK: see
- * psz_amd_last_region. */
+ * manager's decoder knob, the cells' order) can still turn FUSED into FALLBACK (COVER: SLAB): see
+ * psz_amd_last_region.  psz_amd_region_plan is psz_amd_region_plan_mode with
+ * PSZ_AMD_REGION_MODE_WHOLE; a mode that is neither: PSZ_AMD_ERR_INVALID_ARG. */
 int psz_amd_region_plan(const psz_header* h, psz_len origin, psz_len extent, psz_amd_region_info* out);
+int psz_amd_region_plan_mode(const psz_header* h, psz_len origin, psz_len extent, int mode, psz_amd_region_info* out);
 
 int psz_amd_decompress_region_float(psz_resource* m, uint8_t* IN_d_compressed, size_t IN_bytes, psz_len origin,
                                     psz_len extent, float* OUT_d_box);
