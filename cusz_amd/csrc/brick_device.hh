@@ -1,6 +1,6 @@
 // cusz_amd/csrc/brick_device.hh -- what the fused brick kernels for gfx950 share across their
-// translation units (brick_scan.hip, brick_pack.hip, brick_decode.hip, brick_stream.hip).  In the
-// brick pipeline the Lorenzo predictor feeds the Huffman packer (compress) and the Huffman decoder
+// translation units (brick_scan.hip, brick_pack.hip, brick_stream.hip and, with brick_decode.hh on
+// top, brick3_decode.hip, brick1_decode.hip, chunk_decode.hip).  In the brick pipeline the Lorenzo predictor feeds the Huffman packer (compress) and the Huffman decoder
 // feeds the Lorenzo reconstructor directly (decompress).
 //
 // Reference semantics (unchanged, bit-exact): predictor lrz_c.cuhip.inl:275-372 (3D 8^3 tiles),
@@ -23,9 +23,11 @@
 //   pass 2 (brick_pack.hip, k_brick3_pack):  codes (read back, not re-predicted) -> codewords ->
 //                            pack each row (= chunk) into LDS cells -> store at region + running
 //                            offset; par_nbit / par_entry; the unit's outlier slot is copied out.
-//   decompress (brick_decode.hip, k_brick3_decode): one wave per brick, one chunk per lane decoded
-//                            in x-blocks of 32 symbols (f32; 64 for f64) into an LDS code tile; the
-//                            block is reconstructed (reference scan order) and stored as whole rows.
+//   decompress (brick3_decode.hip, k_brick3_decode): one wave per brick, one chunk per lane decoded
+//                            in x-blocks of 64 symbols (32 for an f32 field of at least 12 bricks
+//                            per CU) into an LDS code tile; the block is reconstructed (reference
+//                            scan order) and stored as whole rows.  1-D: brick1_decode.hip; the
+//                            chunk loop they share, decode_chunks4: brick_decode.hh.
 // Single-pass mode (brick_stream.hip: k_brick3_sample, k_brick3_stream, k_brick3_stream_finish):
 // the book comes from a 1/16 sample of 32 x 8 x 8 units before the field is predicted, and one
 // pass -- a workgroup per brick, a wave per y-step -- predicts, sizes (look-back over the bricks)
@@ -166,14 +168,37 @@ int brick_pack_blocks_per_cu();
 
 // Diagnostic build (make prof, psz_amd_debug_brick_profile): the decoders and the single-pass
 // encoder sum per-phase clocks and counts over their waves into 16 counters.  A __device__ array
-// is private to its translation unit, so brick_decode.hip and brick_stream.hip keep one each;
-// psz_amd_debug_brick_profile (brick_decode.hip) returns their sum and resets both.
+// is private to its translation unit, so each unit that counts keeps one, by BPROF_UNIT(fn) at
+// namespace scope: the array, prof_add for a wave to add its counters, and fn, which adds the
+// unit's counters to host[0..15] and clears them when `reset`.  psz_amd_debug_brick_profile
+// (brick3_decode.hip) returns the sum over the units.
 #ifdef CUSZ_AMD_DEC_PROFILE
 #define BPROF(...) __VA_ARGS__
-// adds brick_stream.hip's counters to host[0..15]; clears them when `reset`
-int brick_stream_profile(unsigned long long* host, int reset);
+#define BPROF_UNIT(fn)                                                                             \
+  namespace {                                                                                      \
+  __device__ unsigned long long g_prof[16];                                                        \
+  __device__ __forceinline__ void prof_add(const unsigned long long (&pc)[16], int lane)           \
+  {                                                                                                \
+    if (lane == 0)                                                                                 \
+      for (int i = 0; i < 16; i++) atomicAdd(&g_prof[i], pc[i]);                                   \
+  }                                                                                                \
+  }                                                                                                \
+  int fn(unsigned long long* host, int reset)                                                      \
+  {                                                                                                \
+    unsigned long long c[16] = {};                                                                 \
+    const hipError_t e = hipMemcpyFromSymbol(c, HIP_SYMBOL(g_prof), sizeof(c));                    \
+    for (int i = 0; i < 16; i++) host[i] += c[i];                                                  \
+    const unsigned long long z[16] = {};                                                           \
+    if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z));                          \
+    return (int)e;                                                                                 \
+  }
+int brick3_profile(unsigned long long* host, int reset);        // brick3_decode.hip
+int brick1_profile(unsigned long long* host, int reset);        // brick1_decode.hip
+int chunk_profile(unsigned long long* host, int reset);         // chunk_decode.hip
+int brick_stream_profile(unsigned long long* host, int reset);  // brick_stream.hip
 #else
 #define BPROF(...)
+#define BPROF_UNIT(fn)
 #endif
 
 }  // namespace cusz_amd

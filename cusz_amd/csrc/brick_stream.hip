@@ -4,11 +4,9 @@
 
 namespace cusz_amd {
 
-namespace {
+BPROF_UNIT(brick_stream_profile)  // k_brick3_stream's counters (brick_device.hh)
 
-#ifdef CUSZ_AMD_DEC_PROFILE
-__device__ unsigned long long g_stream_prof[16];  // k_brick3_stream's counters (brick_device.hh BPROF)
-#endif
+namespace {
 
 // =========================================================================================
 // single-pass mode (PSZ_AMD_CODEBOOK_STREAM): sample -> host codebook -> one streaming pass
@@ -500,10 +498,7 @@ k_brick3_stream(const T* __restrict__ in, StreamArgs a, T ebx2_r, T r)
   }
 #undef SPROF
   if (lane == 0 && wbits) atomicAdd(&a.info->total_nbit, wbits);
-#ifdef CUSZ_AMD_DEC_PROFILE
-  if (lane == 0)
-    for (int i = 0; i < 16; i++) atomicAdd(&g_stream_prof[i], pc[i]);
-#endif
+  BPROF(prof_add(pc, lane);)
 }
 
 // after the streaming pass: the outlier segment (the slots in (brick, y-step) order -- brick
@@ -626,19 +621,5 @@ template int launch_brick_stream<float>(const BrickLaunch&, const float*, double
                                         const void*, const void*, hipStream_t, const HostPub&);
 template int launch_brick_stream<double>(const BrickLaunch&, const double*, double, int, bool, const BrickSingle&,
                                          const void*, const void*, hipStream_t, const HostPub&);
-
-#ifdef CUSZ_AMD_DEC_PROFILE
-int brick_stream_profile(unsigned long long* host, int reset)
-{
-  unsigned long long c[16] = {};
-  const hipError_t e = hipMemcpyFromSymbol(c, HIP_SYMBOL(g_stream_prof), sizeof(c));
-  for (int i = 0; i < 16; i++) host[i] += c[i];
-  if (reset) {
-    const unsigned long long z[16] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stream_prof), z, sizeof(z));
-  }
-  return (int)e;
-}
-#endif
 
 }  // namespace cusz_amd

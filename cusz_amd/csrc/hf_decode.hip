@@ -3,7 +3,7 @@
 // into quant codes in index order, and the two decoders that take what the default one does not.
 //
 // launch_hf_decode, at the end of the file, makes the whole choice:
-//  * The default is k_chunk_decode (brick_decode.hip: the fused decoders' chunk loop, lane = chunk,
+//  * The default is k_chunk_decode (chunk_decode.hip: the fused decoders' chunk loop, lane = chunk,
 //    compact per-workgroup tables), for every archive it reads when the decoder knob is AUTO: a
 //    chunk length that is a multiple of 64 and at most 8192, at least one chunk.
 //  * LANE, k_hf_decode_win: one lane decodes a whole chunk, every codeword once; a workgroup's 512

@@ -124,7 +124,7 @@ __device__ __forceinline__ int longest_code(const uint32_t* entry)
   return m;
 }
 
-// ---- decode tables (the fused decoders, brick_decode.hip) ---------------------------------------
+// ---- decode tables (the fused decoders, brick_decode.hh) ----------------------------------------
 // One u32 entry per window, laid out for few instructions per decode step:
 //   [9:0] first symbol, [12:10] 2 x symbols (0, 2 or 4: the tile pointer's advance in bytes),
 //   [25:16] second symbol, [31:27] bits consumed; 0 = "no symbol, no bits" (a code longer than

@@ -227,7 +227,8 @@ template <typename T>
 int launch_spline3_x(SplineXArgs<T> a, const uint32_t* cells, size_t ncell, uint32_t* scratch, hipStream_t st);
 size_t spline_x_scratch_words(uint32_t ntiles, size_t ncell);
 
-// ---- fused brick pipeline (brick_scan / brick_pack / brick_decode / brick_stream .hip) ----------
+// ---- fused brick pipeline (brick_scan / brick_pack / brick_stream / brick3_decode / brick1_decode /
+// chunk_decode .hip) ----------------------------------------------------------------------------
 // A wave owns a W x 8 x 8 brick (W = 64 V); the Huffman chunk length equals W so each brick row
 // is one chunk.  Eligible: 3-D with lx % W == 0, and 1-D (a brick = 64 consecutive chunks, 16
 // tiles of 1024; the last brick and chunk may be short).
@@ -365,9 +366,14 @@ int launch_brick_cell_bounds(const BrickLaunch& L, const uint32_t* cells, size_t
 // decode only, any archive whose chunk length is a multiple of 64: chunk c's codes to
 // codes[sublen c ...] (index order); called through launch_hf_decode
 int launch_chunk_decode(uint32_t ncu, const PhfView& v, uint16_t* codes, size_t n, hipStream_t st);
+// fused decode + reconstruct of a 3-D or 1-D brick field (brick3_decode.hip; 1-D: its half in
+// brick1_decode.hip, launch_brick1_decode)
 template <typename T>
 int launch_brick_decode(const BrickLaunch& L, const PhfView& v, T* out, double eb, int radius, bool zz,
                         const BrickOutliers& ol, hipStream_t st);
+template <typename T>
+int launch_brick1_decode(const BrickLaunch& L, const PhfView& v, T* out, double eb, int radius, bool zz,
+                         const BrickOutliers& ol, hipStream_t st);
 
 // Region decode (3-D brick fields, Lorenzo, ranked cells -- the caller has read the bounds pass's
 // verdict): the box of e elements at o, decoded from its covering bricks only into out_box, a

@@ -356,6 +356,7 @@ struct Pipeline {
   int check_fzg(const psz_header* h, const uint8_t* in, FzgHeader* fh);
   int decode_fzg(const psz_header* h, const uint8_t* in, const FzgHeader& fh);
   int decode_codes(const psz_header* h, const uint8_t* in);
+  int outlier_bounds(const psz_header* h, const uint8_t* in, bool fused, BrickOutliers* ol);
   template <typename T>
   int decompress(const psz_header* h, const uint8_t* in, T* out);
   template <typename T>

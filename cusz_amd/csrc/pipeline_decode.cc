@@ -17,6 +17,15 @@ static bool slab_archive(const psz_header* h)
   return h->pipeline.codec1 == Huffman && h->vle_sublen > 0 && h->vle_pardeg > 0;
 }
 
+// A fused candidate of geometry g, for a region decode by k_brick3_decode (3-D) or k_brick1_decode (1-D)
+// over the covering bricks: Lorenzo behind Huffman chunks of the brick width (256), one per brick row -- the
+// decoder finds a row's chunk by its position.  (An FZG archive has no Huffman chunks to pick bricks by.)
+static bool fused_candidate(const psz_header* h, const BrickGeom& g)
+{
+  return g.ok && g.ndim != 2 && h->pipeline.predictor == Lorenzo && h->pipeline.codec1 == Huffman && h->vle_sublen == g.W &&
+         h->vle_pardeg > 0 && (uint32_t)h->vle_pardeg == g.nchunks && 2 * (int)h->rc.radius <= kMaxBklen;
+}
+
 // What a region decode of an archive with header h touches (psz_amd_region_plan): the header's
 // share of Pipeline::decompress_region's path choice, and the covering bricks.
 // mode (PSZ_AMD_REGION_MODE_*): under COVER every Lorenzo archive that is no fused candidate
@@ -31,22 +40,16 @@ int region_plan(const psz_header* h, psz_len o, psz_len e, int mode, psz_amd_reg
   r.elems = e.x * e.y * e.z;
   const int nd = ndim_of(l);
   const BrickGeom g = brick_geom(nd, l.x, l.y, l.z, h->dtype == F8 ? 8 : 4);
-  // (the decoder finds a brick row's chunk by its position: one chunk per row of 256)
-  // (an FZG archive has no Huffman chunks to pick bricks by: the whole field, then the box)
-  const bool fused = g.ok && nd == 3 && h->pipeline.predictor == Lorenzo && h->pipeline.codec1 == Huffman && h->vle_sublen == g.W &&
-                     h->vle_pardeg > 0 && (uint32_t)h->vle_pardeg == g.nchunks && 2 * (int)h->rc.radius <= kMaxBklen;
-  if (fused) {
-    const RegionBox b = region_box((uint32_t)o.x, (uint32_t)o.y, (uint32_t)o.z, (uint32_t)e.x, (uint32_t)e.y,
-                                   (uint32_t)e.z, (uint32_t)g.W);
+  const bool fused = fused_candidate(h, g) && (nd == 3 || mode == PSZ_AMD_REGION_MODE_COVER);
+  if (fused && nd == 3) {
+    const RegionBox b = region_box((uint32_t)o.x, (uint32_t)o.y, (uint32_t)o.z, (uint32_t)e.x, (uint32_t)e.y, (uint32_t)e.z, (uint32_t)g.W);
     r.path = PSZ_AMD_REGION_FUSED;
     r.brick_lo = psz_len{b.blx, b.bly, b.blz};
     r.brick_n = psz_len{b.bnx, b.bny, b.bnz};
     r.bricks = (size_t)b.bnx * b.bny * b.bnz;
     r.chunks = r.bricks * 64;
   }
-  else if (mode == PSZ_AMD_REGION_MODE_COVER && g.ok && nd == 1 && g.W == 256 && h->pipeline.predictor == Lorenzo &&
-           h->pipeline.codec1 == Huffman && h->vle_sublen == 256 && h->vle_pardeg > 0 &&
-           (uint32_t)h->vle_pardeg == g.nchunks && 2 * (int)h->rc.radius <= kMaxBklen) {
+  else if (fused) {
     // the fused 1-D path (k_brick1_region): the covering tiles of 1024 stand in the brick fields
     const Region1Tiles t = region_tiles1(o.x, e.x);
     r.path = PSZ_AMD_REGION_FUSED;
@@ -112,6 +115,20 @@ int Pipeline::decode_codes(const psz_header* h, const uint8_t* in)
   return PSZ_SUCCESS;
 }
 
+// The bounds pass over the archive's outlier cells (h->splen > 0), and what the reconstructing kernels
+// read of it: cells per brick (fused 3-D), per chunk (fused 1-D) or per reconstruction brick (1-D,
+// not fused).  Advances the cell epoch; the verdict is the word at ol->unsorted.
+int Pipeline::outlier_bounds(const psz_header* h, const uint8_t* in, bool fused, BrickOutliers* ol)
+{
+  const uint32_t nb = !fused ? geom.nbricks : bl.g.ndim == 1 ? bl.g.nchunks : bl.g.nbricks;
+  uint32_t* const flag = d_x1d + nb + 1;
+  *ol = BrickOutliers{reinterpret_cast<const uint32_t*>(in + h->entry[PSZHEADER_SPFMT]), (size_t)h->splen, d_x1d, flag, next_cell_epoch()};
+  CUSZ_AMD_HIP_CHECK((hipError_t)(
+      fused && bl.g.ndim != 1 ? launch_brick_cell_bounds(bl, ol->cells, ol->ncell, d_x1d, flag, ol->epoch, stream)
+                              : launch_x1d_bounds(ol->cells, ol->ncell, n, nb, d_x1d, flag, ol->epoch, stream, fused ? 8 : 14)));
+  return PSZ_SUCCESS;
+}
+
 template <typename T>
 int Pipeline::decompress(const psz_header* h, const uint8_t* in, T* out)
 {
@@ -127,9 +144,9 @@ int Pipeline::decompress(const psz_header* h, const uint8_t* in, T* out)
     if (const int s = check_fzg(h, in, &fh)) return s;
   if (pred == Spline) return decompress_spline<T>(h, in, out);
   mark(kMarkDecBegin);
-  // fused decode + reconstruct (brick_decode.hip): any archive whose chunk length is the brick
-  // width, 3-D and 1-D (2-D linear-brick archives decode chunk by chunk); never an FZG archive,
-  // whatever its vle_sublen says
+  // fused decode + reconstruct (brick3_decode.hip, brick1_decode.hip): any archive whose chunk length is
+  // the brick width, 3-D and 1-D (2-D linear-brick archives decode chunk by chunk); never an FZG archive,
+  // whatever its vle_sublen says.  (Wider than fused_candidate: ZigZag too, vle_pardeg not looked at.)
   const bool brickdec = !fzg && bl.g.ok && bl.g.ndim != 2 && decoder == 0 && h->vle_sublen == bl.g.W &&
                         2 * h->rc.radius <= kMaxBklen;
   const uint32_t* cells = reinterpret_cast<const uint32_t*>(in + h->entry[PSZHEADER_SPFMT]);
@@ -137,17 +154,8 @@ int Pipeline::decompress(const psz_header* h, const uint8_t* in, T* out)
   // decoder ranks each row's zero codes against the brick's cells when they are grouped and
   // sorted; only otherwise does the scatter below run (only_if = unsorted).
   BrickOutliers ol;
-  if (!zz && h->splen && (brickdec || (geom.ndim == 1 && d_x1d))) {
-    // cells per reconstruction brick (1-D, not fused), per chunk (fused 1-D) or per brick (fused 3-D)
-    const uint32_t nb = !brickdec ? geom.nbricks : bl.g.ndim == 1 ? bl.g.nchunks : bl.g.nbricks;
-    if (brickdec && bl.g.ndim != 1)
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_cell_bounds(bl, cells, h->splen, d_x1d, d_x1d + nb + 1,
-                                                              next_cell_epoch(), stream));
-    else
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_x1d_bounds(cells, h->splen, n, nb, d_x1d, d_x1d + nb + 1,
-                                                       next_cell_epoch(), stream, brickdec ? 8 : 14));
-    ol = BrickOutliers{cells, (size_t)h->splen, d_x1d, d_x1d + nb + 1, cell_epoch};
-  }
+  if (!zz && h->splen && (brickdec || (geom.ndim == 1 && d_x1d)))
+    if (const int s = outlier_bounds(h, in, brickdec, &ol)) return s;
   if (zz) CUSZ_AMD_HIP_CHECK(hipMemsetAsync(out, 0, n * sizeof(T), stream));
   CUSZ_AMD_HIP_CHECK((hipError_t)launch_scatter<T>(cells, h->splen, out, n, stream, ol.unsorted, ol.epoch));
   mark(kMarkScatter);
@@ -167,7 +175,7 @@ int Pipeline::decompress(const psz_header* h, const uint8_t* in, T* out)
 }
 
 // The box of e elements at o into `out` (cusz_amd.h psz_amd_decompress_region_*).  FUSED: only
-// the covering bricks are decoded (brick_decode.hip k_brick3_region), which needs the fused 3-D
+// the covering bricks are decoded (brick3_decode.hip k_brick3_region), which needs the fused 3-D
 // decoder's conditions and ranked outlier cells -- the bounds pass's verdict is the one word
 // read back here, before the decode is queued.  FALLBACK: the whole field into a scratch
 // field, then the box copied out.  COVER only: FUSED also for 1-D brick archives (k_brick1_region
@@ -188,21 +196,12 @@ int Pipeline::decompress_region(const psz_header* h, const uint8_t* in, psz_len 
   const bool slab = region_mode == PSZ_AMD_REGION_MODE_COVER && info.path != PSZ_AMD_REGION_FALLBACK &&
                     (h->pipeline.codec1 == FZCodec || h->vle_sublen % 8 == 0);
   BrickOutliers bo;
-  if (fused && h->splen) {
-    const uint32_t* cells = reinterpret_cast<const uint32_t*>(in + h->entry[PSZHEADER_SPFMT]);
-    // cells per brick (3-D) or per chunk (1-D), as the full decompress ranks them
-    const uint32_t nb = ndim == 1 ? bl.g.nchunks : bl.g.nbricks;
-    if (ndim == 1)
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_x1d_bounds(cells, h->splen, n, nb, d_x1d, d_x1d + nb + 1, next_cell_epoch(),
-                                                       stream, 8));
-    else
-      CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_cell_bounds(bl, cells, h->splen, d_x1d, d_x1d + nb + 1,
-                                                              next_cell_epoch(), stream));
+  if (fused && h->splen) {  // (cells per brick or per chunk, as the full decompress ranks them)
+    if (const int s = outlier_bounds(h, in, true, &bo)) return s;
     uint32_t word = 0;
-    CUSZ_AMD_HIP_CHECK(hipMemcpyAsync(&word, d_x1d + nb + 1, 4, hipMemcpyDeviceToHost, stream));
+    CUSZ_AMD_HIP_CHECK(hipMemcpyAsync(&word, bo.unsorted, 4, hipMemcpyDeviceToHost, stream));
     CUSZ_AMD_HIP_CHECK(hipStreamSynchronize(stream));
     fused = word != cell_epoch;
-    bo = BrickOutliers{cells, (size_t)h->splen, d_x1d, d_x1d + nb + 1, cell_epoch};
   }
   if (fused && ndim == 1)  // (COVER only: region_plan)
     CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick1_region<T>(bl, PhfView(h, in), out, h->rc.eb, h->rc.radius, bo, o.x, e.x, stream));

@@ -258,7 +258,7 @@ RING_START_BITS, REFILL_BITS_PER_QUARTER = 8 * 32, 4 * 32 // 2
 
 def quarter_load(census, rows, cap=2047):
     """How hard the given rows of ROW code words (a lane's chunk at sublen 256) drive the compact
-    decoder (brick_decode.hip decode_chunks4) -> (quarters i64[len(rows)], bits i64[len(rows)]).  A lane
+    decoder (brick_decode.hh decode_chunks4) -> (quarters i64[len(rows)], bits i64[len(rows)]).  A lane
     takes up to four table steps per quarter -- a step is one code word, or two first-table words
     of <= 12 bits together -- and a long-class word, found where a table step comes back empty,
     ends the quarter: at most 3 x 16 + 27 = 75 bits.  The lane starts with 8 words in its ring and
@@ -298,7 +298,7 @@ def longest_run(mask):
 def brick_order(ol_idx, dims):
     """Permutation that puts outlier cells in the order the fused 3-D decoders rank them in (the
     order this project's compressor writes): grouped by brick (bz, by, bx), inside a brick by
-    row (y % 8) * 8 + z % 8, then x (brick_decode.hip k_brick_cell_bounds)."""
+    row (y % 8) * 8 + z % 8, then x (brick3_decode.hip k_brick_cell_bounds)."""
     x, y, z = dims
     idx = np.asarray(ol_idx, np.int64)
     gx, gy, gz = idx % x, idx // x % y, idx // (x * y)

@@ -1,4 +1,4 @@
-"""Fused brick path (brick_scan.hip, brick_pack.hip, brick_decode.hip): predictor+encoder and decoder+reconstructor in one pass each.
+"""Fused brick path (brick_scan.hip, brick_pack.hip, brick3_decode.hip, brick1_decode.hip): predictor+encoder and decoder+reconstructor in one pass each.
 
 Parity is the same contract as the reference layout: quant codes (decoded back from the
 archive with the general decoder), outlier set, histogram, codebook, par_nbit and every chunk's

@@ -165,6 +165,50 @@ def test_field_b_has_both_kinds_of_brick():
     assert np.any(counts > 128), counts
 
 
+def test_region_waves_take_a_second_brick():
+    """More covering bricks than the launch has waves (min(CUs, bricks) workgroups of 8): a wave
+    hands over to its next brick -- fetched during the last block, prefetched at its reconstruction
+    -- in the box walk as it does in the field walk; every other box of this file has at most 18
+    bricks.  512 x 256 x 260 f32: 2 x 32 x 33 = 2112 bricks, the last z layer 4 planes deep, some
+    with outlier cells.  The whole field as a box; the box from x = 300 on; and the box from x = 400
+    on, where each brick's first two blocks lie left of the box (they store nothing, and their zero
+    codes still consume the rows' cells).  Field, reference and boxes stay on the device."""
+    import torch
+
+    dims, eb, radius = (512, 256, 260), 1e-3, 512
+    n = int(np.prod(dims))
+    bricks = (dims[0] // 256) * ((dims[1] + 7) // 8) * ((dims[2] + 7) // 8)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert bricks > 8 * cus, (bricks, cus)
+    r = cz.Resource(cz.F4, dims, cz.Lorenzo)
+    d_in = datagen.smooth3d_torch(dims, seed=sum(dims))
+    ptr, nbytes, _ = r.compress(d_in.data_ptr(), eb, cz.Abs, radius)
+    raw = d2h(ptr, nbytes)
+    del d_in
+    h = cz.psz_header.from_buffer_copy(raw[:176].tobytes())
+    idx = raw[h.entry[3]:h.entry[4]].view(np.uint32).reshape(-1, 2)[:, 1].astype(np.int64)
+    of_brick = (idx // (dims[0] * dims[1]) // 8 * 32 + idx // dims[0] % dims[1] // 8) * 2 + idx % dims[0] // 256
+    print(f"{len(np.unique(of_brick))} of {bricks} bricks hold outlier cells ({len(idx)} cells)")
+    assert len(idx) > 0 and of_brick.max() < bricks
+    d_arch = to_device(raw)
+    poison = int(POISON[np.float32])
+    full = torch.full((n,), poison, dtype=torch.int32, device="cuda")
+    r.decompress(d_arch.data_ptr(), nbytes, full.data_ptr())
+    sync()
+    full = full.view(dims[2], dims[1], dims[0])
+    g = GUARD // 4
+    for ox, nbr in ((0, bricks), (300, bricks // 2), (400, bricks // 2)):
+        o, e = (ox, 0, 0), (dims[0] - ox, dims[1], dims[2])
+        nb = int(np.prod(e))
+        buf = torch.full((2 * g + nb,), poison, dtype=torch.int32, device="cuda")
+        r.decompress_region(d_arch.data_ptr(), nbytes, o, e, buf.data_ptr() + GUARD)
+        sync()
+        info = r.last_region()
+        assert info.path == cz.REGION_FUSED and info.bricks == nbr
+        assert torch.equal(buf[g:g + nb].view(e[2], e[1], e[0]), full[:, :, ox:]), ox
+        assert bool((buf[:g] == poison).all()) and bool((buf[g + nb:] == poison).all()), "written outside the box"
+
+
 FALLBACK_BOXES = {
     "1d": ((12_345, 0, 0), (20_001, 1, 1)),
     "2d": ((17, 5, 0), (250, 30, 1)),

@@ -1,6 +1,6 @@
 """1-D reconstruction reading the outlier values straight from the archive's cells: the
 reference layout's k_lorenzo_x1d (BrickOutliers,per 16384-element brick) and the fused 1-D brick
-decoder (brick_decode.hip k_brick1_decode, per chunk).  Sorted cells (no spill) take that path, cells
+decoder (brick1_decode.hip k_brick1_decode, per chunk).  Sorted cells (no spill) take that path, cells
 with a spill tail (one brick over its slot) fall back to the scatter.  Both must equal the
 oracle's decompression bit for bit (run_roundtrip), and a shuffled cell list must decompress
 identically.
