@@ -178,6 +178,9 @@ int launch_zero(const XferRegions& r, hipStream_t st);  // dst/nwords only
 int launch_book_device(const uint32_t* hist, int bklen, uint32_t smooth, uint32_t* book, uint8_t* revbook,
                        hipStream_t st);
 int launch_excess(const uint32_t* spill_cnt, uint32_t cap, uint32_t* dst, hipStream_t st);
+// a caller's histogram (bklen counts + the overflow word) over the scan's own, in place; a bin the
+// caller left 0 that the scan counted takes weight 1 and raises *missing
+int launch_take_hist(const uint32_t* ext, uint32_t* hist, int bklen, unsigned int* missing, hipStream_t st);
 
 // ---- cuSZ-i spline3 (spline.hip) -----------------------------------------------------------
 struct SplineGeom {

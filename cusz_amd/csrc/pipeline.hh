@@ -105,7 +105,8 @@ struct Event {  // likewise
 // of every compress; the tickets are the 9-word publish tickets of pub_device.hh.
 struct SmallBuf {
   uint32_t spill_cnt, pad0[3];
-  unsigned int timeout, code_lost, pad1[10];  // code_lost: spline codes no outlier cell can carry
+  unsigned int timeout, code_lost, hist_missing, pad1[9];  // code_lost: spline codes no outlier cell can carry;
+                                                           // hist_missing: a caller's histogram lacks a used bin
   CompressInfo info;
   uint32_t plan_ticket[9], pad2[3];
   uint32_t hist_ticket[9];
@@ -121,7 +122,7 @@ struct SmallBuf {
 constexpr size_t kSmallBytes = sizeof(SmallBuf);
 constexpr size_t kSmallZeroBytes = offsetof(SmallBuf, summary_ticket) + sizeof(SmallBuf::summary_ticket);
 static_assert(offsetof(SmallBuf, spill_cnt) == 0 && offsetof(SmallBuf, timeout) == 16 && offsetof(SmallBuf, code_lost) == 20 &&
-                  offsetof(SmallBuf, info) == 64 &&
+                  offsetof(SmallBuf, hist_missing) == 24 && offsetof(SmallBuf, info) == 64 &&
                   offsetof(SmallBuf, plan_ticket) == 112 && offsetof(SmallBuf, hist_ticket) == 160 &&
                   offsetof(SmallBuf, summary_ticket) == 196 && offsetof(SmallBuf, book_flag) == 240 &&
                   offsetof(SmallBuf, minmax) == 256 && offsetof(SmallBuf, ext_scratch) == 512 &&
@@ -135,12 +136,13 @@ struct Readback {
   uint8_t header[sizeof(psz_header)], pad0[80];  // the archive's psz header
   CompressInfo info;
   uint8_t pad1[80];
-  unsigned int timeout, code_lost, pad2[14];  // read back together (SmallBuf keeps them adjacent)
+  unsigned int timeout, code_lost, hist_missing, pad2[13];  // read back together (SmallBuf keeps them adjacent;
+                                                            // hist_missing with a caller's histogram only)
   uint32_t excess, pad3[15];  // a sharded finish's summed overflow word
   double minmax[2];           // Rel mode's extrema
 };
 static_assert(offsetof(Readback, header) == 0 && offsetof(Readback, info) == 256 && offsetof(Readback, timeout) == 384 &&
-                  offsetof(Readback, code_lost) == 388 &&
+                  offsetof(Readback, code_lost) == 388 && offsetof(Readback, hist_missing) == 392 &&
                   offsetof(Readback, excess) == 448 && offsetof(Readback, minmax) == 512 && sizeof(Readback) <= 1024,
               "read-back layout");
 
@@ -252,6 +254,7 @@ struct Pipeline {
 
   uint32_t* spill_cnt() { return &d_small.p->spill_cnt; }
   unsigned int* timeout() { return &d_small.p->timeout; }
+  unsigned int* hist_missing() { return &d_small.p->hist_missing; }
   CompressInfo* info() { return &d_small.p->info; }
   double* minmax() { return d_small.p->minmax; }
   unsigned int* ext_scratch() { return d_small.p->ext_scratch; }

@@ -119,13 +119,13 @@ XferRegions Pipeline::hist_regions(int bklen)
   return r;
 }
 
-// header + summary; a sharded finish also reads back the summed overflow word (the device-book
-// path sends no histogram to the host)
+// header + summary; a sharded finish also reads back the word k_take_hist raises and the summed
+// overflow word (the device-book path sends no histogram to the host)
 XferRegions Pipeline::readback_regions()
 {
   Readback* rb = h_readback();
   XferRegions r = regions({{rb->header, d_archive, sizeof(psz_header)}, {&rb->info, info(), sizeof(CompressInfo)},
-                           {&rb->timeout, timeout(), 8}, {&rb->excess, d_hist + 2 * pend.radius, 4}});
+                           {&rb->timeout, timeout(), pend.ext ? 12u : 8u}, {&rb->excess, d_hist + 2 * pend.radius, 4}});
   r.count = pend.ext ? 4 : 3;
   return r;
 }
@@ -256,8 +256,14 @@ int Pipeline::compress_finish(psz_header* h, const uint32_t* ext_hist, uint8_t**
   pend.active = false;
   pend.ext = ext_hist != nullptr;
   if (ext_hist) {
-    // bklen counts + the summed overflow word of every slab (psz_amd_compress_scan_*)
-    CUSZ_AMD_HIP_CHECK(hipMemcpyAsync(d_hist, ext_hist, (size_t)(2 * pend.radius + 1) * 4, hipMemcpyDeviceToDevice, stream));
+    // bklen counts + the summed overflow word of every slab (psz_amd_compress_scan_*).  FZG builds
+    // no book (only the overflow word counts); every other path checks the counts against the
+    // scan's own on the way in (k_take_hist), and finish_compress refuses a histogram that lacks
+    // a bin this slab uses
+    if (pend.path == Path::Fzg)
+      CUSZ_AMD_HIP_CHECK(hipMemcpyAsync(d_hist, ext_hist, (size_t)(2 * pend.radius + 1) * 4, hipMemcpyDeviceToDevice, stream));
+    else
+      CUSZ_AMD_HIP_CHECK((hipError_t)launch_take_hist(ext_hist, d_hist, 2 * pend.radius, hist_missing(), stream));
     pend.hist_epoch = 0;  // the scan's published histogram is not the one to encode with
   }
   switch (pend.path) {
@@ -455,6 +461,12 @@ int Pipeline::finish_compress(psz_header* h, uint8_t** out, size_t* outlen)
   if (tmo) {
     std::fprintf(stderr, "[cusz_amd] encoder reservation/look-back check failed\n");
     return PSZ_AMD_ERR_ENCODER;
+  }
+  // the caller's histogram had a zero bin for a symbol this slab uses (a wrong reduction): the
+  // encode ran on a book that gives that symbol weight 1, and its archive is not handed out
+  if (pend.ext && rb->hist_missing) {
+    pend.ext = false;
+    return PSZ_AMD_ERR_INVALID_ARG;
   }
   // spline: some point's code is past what an outlier cell carries (cusz_amd.h): decompression
   // could not reproduce the compressor's codes, so no archive is handed back

@@ -393,6 +393,31 @@ int launch_excess(const uint32_t* spill_cnt, uint32_t cap, uint32_t* dst, hipStr
   return (int)hipGetLastError();
 }
 
+// A sharded finish takes the caller's reduced histogram ext (bklen counts + the overflow word) in
+// place of the scan's own, hist.  A sum over slabs can only be larger than this slab's counts: a
+// bin that is 0 in ext and counted in hist means the caller's reduction is wrong, and the book of
+// ext would give that symbol no codeword (the encoders would pack the unused-symbol word).  Such a
+// bin takes weight 1, so that the book stays encodable, and *missing is raised: the finish reports
+// it from the summary read-back and hands no archive out.
+__global__ void __launch_bounds__(256) k_take_hist(const uint32_t* __restrict__ ext, uint32_t* __restrict__ hist, int bklen,
+                                                   unsigned int* missing)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i > bklen) return;
+  uint32_t e = ext[i];
+  if (i < bklen && e == 0u && hist[i] != 0u) {
+    e = 1u;
+    atomicOr(missing, 1u);
+  }
+  hist[i] = e;
+}
+
+int launch_take_hist(const uint32_t* ext, uint32_t* hist, int bklen, unsigned int* missing, hipStream_t st)
+{
+  k_take_hist<<<(bklen + 1 + 255) / 256, 256, 0, st>>>(ext, hist, bklen, missing);
+  return (int)hipGetLastError();
+}
+
 int launch_upload(const XferRegions& r, hipStream_t st)
 {
   k_upload<<<4, 256, 0, st>>>(r);

@@ -180,6 +180,14 @@ int psz_amd_set_codebook(psz_resource* m, int mode);
  *      word is nonzero (some slab had more outliers than its capacity: past the reference's
  *      10 %), every slab's finish returns PSZ_WARN_OUTLIER_TOO_MANY, the slabs that overflowed
  *      have grown their capacity, and repeating steps 1-3 succeeds on every rank together.
+ *      IN_d_hist must count every symbol this slab uses: a bin that is 0 where the slab's own
+ *      pass-1 histogram is not (a sum over slabs cannot be; a wrong reduction can) would leave a
+ *      used symbol without a codeword, so the finish returns PSZ_AMD_ERR_INVALID_ARG, leaves
+ *      OUT_d_compressed and OUT_compressed_bytes untouched and consumes the pending scan; the
+ *      manager stays usable (scan again, finish with the right histogram).  Any other relation
+ *      between the two histograms is accepted -- counts smaller than the slab's own included,
+ *      as long as they are nonzero.  The check runs on the device and costs no host wait; FZG
+ *      archives, which use no codebook, are exempt, spline archives are not.
  * psz_compress_analyize_float (cusz_rev1.h) is step 1 with the histogram exported to the host
  * (compressor.inl:305-337). */
 int psz_amd_compress_scan_float(psz_resource* m, psz_rc2 rc, float* IN_d_data, uint32_t* OUT_d_hist);
