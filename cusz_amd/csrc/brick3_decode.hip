@@ -241,7 +241,12 @@ __device__ __forceinline__ T from_lower_half(T x)
 // from a start value, -0.0 in the lower half (-0.0 + v == v for every v, so s_0 = v_0 exactly)
 // and, in the upper half, the lower half's s_3 of the same column (v_permlane32_swap).
 // Outliers: as recon_block, each row's zero codes ranked among the 32 lanes of its half.
-template <typename T, bool ZZ, bool BUF, int TP, bool CELLS>
+// FULL (the caller's wave-uniform nyv == 8 && nzv == 8, every brick of a field whose y and z
+// extents are multiples of 8): no row or plane test anywhere, the four row descriptors and the
+// plane offsets formed once, and the sums, scans and 32 stores of the block in one straight
+// line -- the same IEEE operations in the same order, two z rows per packed instruction where
+// the operands pair up (as recon_block: the y sums, the z steps d = 2, 4, the scale).
+template <typename T, bool ZZ, bool BUF, int TP, bool CELLS, bool FULL>
 __device__ __forceinline__ void recon_block32(const uint16_t* tile, T* out, size_t plane, uint32_t lx, uint32_t nyv,
                                               uint32_t nzv, size_t base_elem, T r, T ebx2, int lane,
                                               const BrickCells* bc = nullptr)
@@ -250,11 +255,12 @@ __device__ __forceinline__ void recon_block32(const uint16_t* tile, T* out, size
   const uint32_t hl = (uint32_t)lane >> 5, l32 = (uint32_t)lane & 31u;
   const uint32_t col = rcol(l32);
   const uint32_t ybase = 4u * hl;
+  if constexpr (FULL) nzv = 8u;
   T v[4][8];
 #pragma unroll
   for (int yy = 0; yy < 4; yy++) {
     const uint32_t y = ybase + (uint32_t)yy;
-    const bool yok = y < nyv;
+    const bool yok = FULL || y < nyv;
     uint32_t cd[8];
 #pragma unroll
     for (int z = 0; z < 8; z++) cd[z] = tile[(y * 8 + (uint32_t)z) * TP + col];
@@ -294,6 +300,67 @@ __device__ __forceinline__ void recon_block32(const uint16_t* tile, T* out, size
         }
       }
     }
+  }
+  if constexpr (FULL && sizeof(T) == 4) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    // y running sums: the lower half's s_3 (computed by every lane, used by the upper half)
+    f2 c[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      f2 u = {v[0][2 * j], v[0][2 * j + 1]};
+#pragma unroll
+      for (int yy = 1; yy < 4; yy++) u = u + f2{v[yy][2 * j], v[yy][2 * j + 1]};
+      c[j] = f2{from_lower_half<T>(u.x), from_lower_half<T>(u.y)};
+    }
+    const uint32_t voff = (col + hl * 4u * lx) * (uint32_t)sizeof(T);
+    f2 scale = {(float)ebx2, (float)ebx2};
+    asm("" : "+s"(scale));  // one scalar pair for every v_pk_mul_f32, not one per use
+    __amdgpu_buffer_rsrc_t ro[4];
+    uint32_t soff[8];
+    if constexpr (BUF) {
+#pragma unroll
+      for (int yy = 0; yy < 4; yy++) ro[yy] = rsrc(base + (size_t)yy * lx);
+#pragma unroll
+      for (int z = 0; z < 8; z++) soff[z] = (uint32_t)((size_t)z * plane * sizeof(T));
+    }
+#pragma unroll
+    for (int yy = 0; yy < 4; yy++) {
+      T t[8];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        c[j] = c[j] + f2{v[yy][2 * j], v[yy][2 * j + 1]};
+        t[2 * j] = c[j].x, t[2 * j + 1] = c[j].y;
+      }
+      // x Hillis-Steele, step by step over the eight independent z rows (x_scan8i's steps)
+#pragma unroll
+      for (int z = 0; z < 8; z++) t[z] = t[z] + dpp0<0x112>(t[z]), no_slp(t[z]);  // column x - 1
+#pragma unroll
+      for (int z = 0; z < 8; z++) t[z] = t[z] + dpp0<0x114>(t[z]), no_slp(t[z]);  // column x - 2
+#pragma unroll
+      for (int z = 0; z < 8; z++) t[z] = t[z] + dpp0<0x118>(t[z]), no_slp(t[z]);  // column x - 4
+#pragma unroll
+      for (int z = 7; z >= 1; z--) t[z] = t[z] + t[z - 1];
+      f2 tp[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) tp[j] = f2{t[2 * j], t[2 * j + 1]};
+      tp[3] = tp[3] + tp[2], tp[2] = tp[2] + tp[1], tp[1] = tp[1] + tp[0];  // d = 2 (descending)
+      tp[3] = tp[3] + tp[1], tp[2] = tp[2] + tp[0];                          // d = 4
+#pragma unroll
+      for (int j = 0; j < 4; j++) tp[j] = tp[j] * scale;
+#pragma unroll
+      for (int j = 0; j < 4; j++) t[2 * j] = tp[j].x, t[2 * j + 1] = tp[j].y;
+      if constexpr (BUF) {
+#pragma unroll
+        for (int z = 0; z < 8; z++) buf_store<T>(t[z], ro[yy], voff, soff[z]);
+      }
+      else {
+        // wave-uniform row address plus the lane's 32-bit byte offset (no 64-bit lane addresses)
+#pragma unroll
+        for (int z = 0; z < 8; z++)
+          *reinterpret_cast<T*>(reinterpret_cast<char*>(base + (size_t)z * plane + (size_t)yy * lx) + (size_t)voff) = t[z];
+      }
+    }
+    return;
   }
   // y running sums: the lower half's s_3 (computed by every lane, used by the upper half)
   T c[8];
@@ -552,10 +619,21 @@ k_brick3_decode(const uint32_t* __restrict__ bitstream, uint32_t bs_words, const
             recon_block<T, ZZ, BUF, C::TP, false>(tile, out, plane, lx, nyv, nzv, base_elem, r, ebx2, lane);
         }
         else {
-          if (ranked)
-            recon_block32<T, ZZ, BUF, C::TP, true>(tile, out, plane, lx, nyv, nzv, base_elem, r, ebx2, lane, &bc);
-          else
-            recon_block32<T, ZZ, BUF, C::TP, false>(tile, out, plane, lx, nyv, nzv, base_elem, r, ebx2, lane);
+          // full bricks (every one of a field with y and z extents in multiples of 8) take the
+          // straight-line body: one wave-uniform choice per block
+          auto go = [&](auto cells, auto full) {
+            recon_block32<T, ZZ, BUF, C::TP, decltype(cells)::value, decltype(full)::value>(tile, out, plane, lx, nyv, nzv, base_elem, r,
+                                                                                          ebx2, lane, &bc);
+          };
+          const bool full = nyv == 8u && nzv == 8u;
+          if (ranked) {
+            if (full) go(std::true_type{}, std::true_type{});
+            else go(std::true_type{}, std::false_type{});
+          }
+          else {
+            if (full) go(std::false_type{}, std::true_type{});
+            else go(std::false_type{}, std::false_type{});
+          }
         }
       }
     };
