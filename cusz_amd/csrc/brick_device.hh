@@ -7,22 +7,25 @@
 // reconstruct lrz_x.cuhip.inl:271-360, histogram hist.cuhip.inl:55-89, chunked MSB-first
 // Huffman cells hf_kernels.cuhip.inl:97-157, canonical decode hf_kernels.cuhip.inl:331-396.
 //
-// MI355X layout.  A wave owns a brick of W x 8 x 8 elements (W = 64 V: lane l holds x in
-// [l V, l V + V)).  The Huffman chunk length is W, so every brick ROW (fixed y, z) is exactly one
-// reference chunk: chunk c covers codes [c W, c W + W) of the linear (x-fastest) order.
+// MI355X layout.  A wave owns a brick of W x 8 x 8 elements (W = 64 V, V = 4: kBrickW, kBrickV;
+// lane l holds x in [l V, l V + V)), in both encode passes: one histogram record (u16 counts: a
+// brick has 16384 elements), one outlier slot and one reserved bitstream region per brick.  The
+// Huffman chunk length is W, so every brick ROW (fixed y, z) is exactly one reference chunk:
+// chunk c covers codes [c W, c W + W) of the linear (x-fastest) order.
 //   pass 1 (brick_scan.hip, k_brick3_scan):  predict -> codes in brick order (byte rows; u16 rows
-//                            when a code leaves the byte window, one mask bit per row), per-unit
+//                            when a code leaves the byte window, one mask bit per row), per-brick
 //                            histogram (u16, kept for the plan), global histogram, outlier slots.
 //                            Reads the input once.
 //   host:                    canonical codebook from the global histogram (exact reference heap).
-//   plan (brick_pack.hip, k_brick_plan):  a unit's bits = sum(hist_u[s] * len[s]); its region in
+//   plan (brick_pack.hip, k_brick_plan):  a brick's bits = sum(hist_b[s] * len[s]); its region in
 //                            the bitstream is that many bits plus one partial cell per row -- an
-//                            upper bound, known BEFORE encoding, so every unit writes at a fixed
+//                            upper bound, known BEFORE encoding, so every brick writes at a fixed
 //                            offset: no look-back, no scratch, no gather.  The last block writes
 //                            the headers.
-//   pass 2 (brick_pack.hip, k_brick3_pack):  codes (read back, not re-predicted) -> codewords ->
-//                            pack each row (= chunk) into LDS cells -> store at region + running
-//                            offset; par_nbit / par_entry; the unit's outlier slot is copied out.
+//   pass 2 (brick_pack.hip, k_brick3_pack):  bricks last to first; codes (read back, not
+//                            re-predicted) -> codewords -> pack each row (= chunk) into LDS cells
+//                            -> store at region + running offset; par_nbit / par_entry; the
+//                            brick's outlier slot is copied out.
 //   decompress (brick3_decode.hip, k_brick3_decode): one wave per brick, one chunk per lane decoded
 //                            in x-blocks of 64 symbols (32 for an f32 field of at least 12 bricks
 //                            per CU) into an LDS code tile; the block is reconstructed (reference
@@ -56,13 +59,10 @@ using namespace lrzd;
 namespace {
 
 constexpr int kBrickWaves = 4;  // waves per workgroup in the encode passes
+constexpr int kBrickV = 4, kBrickW = 64 * kBrickV;  // elements per lane and per brick row (BrickGeom::V, W)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kBufRsrcW3 = 0x00020000;  // raw buffer resource word 3 (gfx9)
 constexpr uint32_t kOOB = 0x80000000u;       // buffer offset past any range: the load returns 0
-// A unit = kUnitBricks consecutive bricks, processed by one wave in both encode passes: one
-// histogram record (u16 counts: a unit has at most 32768 elements), one outlier slot and one
-// reserved bitstream region per unit.
-constexpr int kUnitBricks = 1;
 
 __device__ __forceinline__ uint32_t readlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 
@@ -70,74 +70,83 @@ __device__ __forceinline__ uint32_t readlane(uint32_t v, int l) { return (uint32
 // (config 2 pass 1 189 -> 163 us: the streamed field no longer evicts the code rows pass 2 reads)
 constexpr int kScanLoadAux = 2;
 
+// a lane's four elements of a row at byte offset `off` of a raw buffer: one 16-B load (f64: two);
+// an offset past the range reads 0 and touches no memory
+template <typename T, int AUX>
+__device__ __forceinline__ void buffer_load4(__amdgpu_buffer_rsrc_t rs, uint32_t off, T (&dst)[kBrickV])
+{
+#pragma unroll
+  for (int h = 0; h < (int)(kBrickV * sizeof(T) / 16); h++) {
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off + 16 * h), 0, AUX);
+    __builtin_memcpy(reinterpret_cast<char*>(&dst[0]) + 16 * h, &v, 16);
+  }
+}
+
 // The rows of a brick, for the encoders that stream the field brick by brick (pass 1 and the
 // single-pass encoder): raw buffer loads from the brick's origin, issued ahead of their use and
-// across brick boundaries.
-template <typename T, int V>
+// across brick boundaries.  The brick's address work is done once (rows_of: its coordinates, the
+// 64-bit origin, the descriptor); a row takes its in-brick offset and two compares.  That saves
+// work in pass 1, whose rolled row loop would redo the brick's part every y-step; the single-pass
+// encoder issues its eight rows in one straight line, where the compiler shares that part anyway,
+// and uses the same pair for the one code path, at no measured gain.  Straight-line code: no
+// per-row branches, so the waitcnt pass can count the loads exactly.
+template <typename T>
 struct StepLoader {
   const T* in;
   size_t plane;
   uint32_t lx, ly, lz, nbx, nby, nbricks;
-  int reverse;
   uint32_t lane;
-  __device__ __forceinline__ uint32_t brick_of(uint32_t it) const { return reverse ? nbricks - 1 - it : it; }
-  // Rows (y, z = 0..7) of brick `it` by raw buffer loads from the brick's origin: one 16-B (f64:
-  // two) load per lane and row, rows outside the field get an offset past the range and read 0.
-  // Straight-line code: no per-row branches, so the waitcnt pass can count the loads exactly.
-  // row `row` = 8 y + z of brick `it` (rows outside the field read 0)
-  __device__ __forceinline__ void issue_row(uint32_t it, int row, T (&dst)[V]) const
-  {
-    // past the last brick the load still issues (at brick 0's origin, past the range: reads 0,
-    // touches no memory): every path issues the same loads, so the compiler counts the waits
-    // (vmcnt(7) for the row loaded 8 rows ago, not vmcnt(0): compress -3 us, 1-D -9 us)
-    const bool live = it < nbricks;
-    const uint32_t b = live ? brick_of(it) : 0u, bx = b % nbx, t = b / nbx, by = t % nby, bz = t / nby;
-    const T* origin = in + (size_t)bz * 8 * plane + (size_t)by * 8 * lx + (size_t)bx * (64 * V);
-    const uint32_t span = (uint32_t)(8 * plane * sizeof(T));  // < 2^31 (brick_geom)
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(origin), 0, (int)span, (int)kBufRsrcW3);
-    const uint32_t y = (uint32_t)row >> 3, z = (uint32_t)row & 7u;
-    const bool ok = live && by * 8 + y < ly && bz * 8 + z < lz;
-    const uint32_t off =
-        ok ? (uint32_t)(((size_t)z * plane + (size_t)y * lx) * sizeof(T)) + lane * (V * sizeof(T)) : span;
-#pragma unroll
-    for (int h = 0; h < (int)(V * sizeof(T) / 16); h++) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off + 16 * h), 0, kScanLoadAux);
-      __builtin_memcpy(reinterpret_cast<char*>(&dst[0]) + 16 * h, &v, 16);
-    }
-  }
-  // The same loads with the brick's address work done once per brick (BrickRows): per row only
-  // the in-brick offset and two compares, instead of the brick coordinates, the 64-bit origin and
-  // the descriptor again for every row (pass 1: ~50 scalar instructions and the SGPR spills they
-  // cause, per row).
   struct BrickRows {
     __amdgpu_buffer_rsrc_t rs;  // at the brick's origin, 8 planes long
     uint32_t nyv, nzv;          // rows y < nyv, z < nzv lie in the field (0: past the last brick)
   };
-  __device__ __forceinline__ BrickRows rows_of(uint32_t it) const
+  // past the last brick the loads still issue (at brick 0's origin, past the range: they read 0
+  // and touch no memory): every path issues the same loads, so the compiler counts the waits
+  // (vmcnt(7) for the row loaded 8 rows ago, not vmcnt(0): compress -3 us, 1-D -9 us)
+  __device__ __forceinline__ BrickRows rows_of(uint32_t brick) const
   {
-    const bool live = it < nbricks;
-    const uint32_t b = live ? brick_of(it) : 0u, bx = b % nbx, t = b / nbx, by = t % nby, bz = t / nby;
-    const T* origin = in + (size_t)bz * 8 * plane + (size_t)by * 8 * lx + (size_t)bx * (64 * V);
+    const bool live = brick < nbricks;
+    const uint32_t b = live ? brick : 0u, bx = b % nbx, t = b / nbx, by = t % nby, bz = t / nby;
+    const T* origin = in + (size_t)bz * 8 * plane + (size_t)by * 8 * lx + (size_t)bx * kBrickW;
     const uint32_t span = (uint32_t)(8 * plane * sizeof(T));  // < 2^31 (brick_geom)
     return {__builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(origin), 0, (int)span, (int)kBufRsrcW3),
             live ? min(8u, ly - by * 8) : 0u, live ? min(8u, lz - bz * 8) : 0u};
   }
-  __device__ __forceinline__ void issue_row(const BrickRows& br, uint32_t y, uint32_t z, T (&dst)[V]) const
+  // row (y, z) of the brick; rows outside the field get an offset past the range and read 0
+  __device__ __forceinline__ void issue_row(const BrickRows& br, uint32_t y, uint32_t z, T (&dst)[kBrickV]) const
   {
     const uint32_t span = (uint32_t)(8 * plane * sizeof(T));
     const bool ok = y < br.nyv && z < br.nzv;
-    const uint32_t off = ok ? (z * (uint32_t)plane + y * lx) * (uint32_t)sizeof(T) + lane * (V * sizeof(T)) : span;
-#pragma unroll
-    for (int h = 0; h < (int)(V * sizeof(T) / 16); h++) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(br.rs, (int)(off + 16 * h), 0, kScanLoadAux);
-      __builtin_memcpy(reinterpret_cast<char*>(&dst[0]) + 16 * h, &v, 16);
-    }
+    const uint32_t off = ok ? (z * (uint32_t)plane + y * lx) * (uint32_t)sizeof(T) + lane * (kBrickV * sizeof(T)) : span;
+    buffer_load4<T, kScanLoadAux>(br.rs, off, dst);
+  }
+};
+
+// The same two steps for linear bricks (1-D and 2-D pass 1): brick b is elements [b 64 W,
+// (b + 1) 64 W) of the field, row r its r-th W.  The descriptor ends with the field, so rows past
+// its end, and every row past the last brick (brick 0 with an empty range), read 0.
+template <typename T>
+struct LinearLoader {
+  static constexpr uint32_t kBrickElems = 64 * kBrickW;
+  const T* in;
+  size_t n;
+  uint32_t nbricks, lane;
+  __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_of(uint32_t brick) const
+  {
+    const bool live = brick < nbricks;
+    const size_t o = live ? (size_t)brick * kBrickElems : 0;
+    const uint32_t span = live ? (uint32_t)(min((size_t)kBrickElems, n - o) * sizeof(T)) : 0u;
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(in + o), 0, (int)span, (int)kBufRsrcW3);
+  }
+  __device__ __forceinline__ void issue_row(__amdgpu_buffer_rsrc_t rs, int row, T (&dst)[kBrickV]) const
+  {
+    buffer_load4<T, kScanLoadAux>(rs, ((uint32_t)row * kBrickW + lane * kBrickV) * (uint32_t)sizeof(T), dst);
   }
 };
 
 // Row packing (hfd::pack4_or_lj / hfd::pack_words into a wave's LDS cells), pass 2 and the
 // single-pass encoder:
-constexpr int kPackRowMax = (64 * 4 * kLmax + 31) / 32 + 2;  // words one row's packing may touch
+constexpr int kPackRowMax = (kBrickW * kLmax + 31) / 32 + 2;  // words one row's packing may touch
 
 // four consecutive elements (16 B for f32, 32 B for f64) to / from 16-B aligned LDS
 template <typename T>

@@ -80,24 +80,10 @@ k_brick3_sample(const T* __restrict__ in, uint32_t lx, uint32_t ly, uint32_t lz,
       const bool ok = y < ly && z0 + (uint32_t)z < lz;
       load_row<T, 4>(in, (size_t)(z0 + z) * plane + (size_t)y * lx, x0, lx, ok, v[z]);
     }
-    // prequant, z-diff, x-diff inside the 8-wide tile (two lanes), y-diff across lanes (the
-    // reference's order, lrz_c.cuhip.inl:341-352)
+    // prequant, z-diff, x-diff inside the 8-wide tile (two lanes), then the y-diff across lanes
     T a[8][4], pp[4];
 #pragma unroll
-    for (int z = 0; z < 8; z++)
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const T p = dround(v[z][k] * ebx2_r);
-        a[z][k] = z > 0 ? p - pp[k] : p;
-        pp[k] = p;
-      }
-#pragma unroll
-    for (int z = 0; z < 8; z++) {
-      const T west = shr_in_tile<T, 1, 2>(a[z][3]);
-#pragma unroll
-      for (int k = 3; k > 0; k--) a[z][k] = a[z][k] - a[z][k - 1];
-      if (lane & 1) a[z][0] = a[z][0] - west;
-    }
+    for (int z = 0; z < 8; z++) residual_zx(v[z], ebx2_r, z == 0, !(lane & 1), pp, a[z]);
 #pragma unroll
     for (int z = 0; z < 8; z++) {
       const bool ok = y < ly && z0 + (uint32_t)z < lz;
@@ -201,7 +187,7 @@ constexpr int kStreamWaves = 8;  // one wave per y-step of the brick
 // through an exchange area; every wave stages its y-step's packed cells in a staging area until
 // the brick's offset is known (one brick later: the look-back is deferred)
 template <typename T>
-constexpr int kStreamXsWords = 8 * 64 * 4 * (int)sizeof(T) / 4;
+constexpr int kStreamXsWords = 8 * kBrickW * (int)sizeof(T) / 4;
 constexpr int kStageW = 512;  // staging words per wave
 static_assert(kStageW >= 2 * kPackRowMax + 2, "the flush path holds two rows");
 template <typename T>
@@ -226,7 +212,7 @@ __global__ void __launch_bounds__(64 * kStreamWaves)
 __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 4 : 2)))  // f32: 2 workgroups per CU (LDS, 128 VGPRs)
 k_brick3_stream(const T* __restrict__ in, StreamArgs a, T ebx2_r, T r)
 {
-  constexpr int V = 4;
+  constexpr int V = kBrickV, W = kBrickW;
   constexpr int XW = kStreamXsWords<T>;
   extern __shared__ uint32_t smem[];  // exchange areas (waves 0..6), then staging areas
   __shared__ uint32_t s_book[kMaxBklen];
@@ -236,7 +222,7 @@ k_brick3_stream(const T* __restrict__ in, StreamArgs a, T ebx2_r, T r)
   T* const xsT = reinterpret_cast<T*>(smem + (wid < kStreamWaves - 1 ? wid : 0) * XW);
   const T* const xprev = reinterpret_cast<const T*>(smem + (wid > 0 ? wid - 1 : 0) * XW);
   uint32_t* const stg = smem + (kStreamWaves - 1) * XW + wid * kStageW;
-  const StepLoader<T, V> ld{in, (size_t)a.lx * a.ly, a.lx, a.ly, a.lz, a.nbx, a.nby, a.nbricks, 0, (uint32_t)lane};
+  const StepLoader<T> ld{in, (size_t)a.lx * a.ly, a.lx, a.ly, a.lz, a.nbx, a.nby, a.nbricks, (uint32_t)lane};
   const uint32_t subcap = a.ol.cap_per_brick;
 
   // workgroup 0, wave 0: the host's codebook -> device memory and the archive, then the flag
@@ -266,8 +252,11 @@ k_brick3_stream(const T* __restrict__ in, StreamArgs a, T ebx2_r, T r)
   __syncthreads();
   uint32_t brick = s_next[0];
   T q[8][V];  // this wave's rows of the brick (loaded one brick ahead)
+  {
+    const auto br = ld.rows_of(brick);
 #pragma unroll
-  for (int z = 0; z < 8; z++) ld.issue_row(brick, 8 * wid + z, q[z]);
+    for (int z = 0; z < 8; z++) ld.issue_row(br, (uint32_t)wid, (uint32_t)z, q[z]);
+  }
   bool have_book = false;
   unsigned long long wbits = 0;  // bits this wave packed (the header's total)
   uint32_t par = 0;
@@ -285,7 +274,7 @@ k_brick3_stream(const T* __restrict__ in, StreamArgs a, T ebx2_r, T r)
     if (!live && dbrick == kNoBrick) break;
     BPROF(pc[0] += live;)
     const uint32_t bx = brick % a.nbx, t = brick / a.nbx, by = t % a.nby, bz = t / a.nby;
-    const uint32_t x0 = bx * (64 * V) + lane * V, z0 = bz * 8, gy = by * 8 + (uint32_t)wid;
+    const uint32_t x0 = bx * W + lane * V, z0 = bz * 8, gy = by * 8 + (uint32_t)wid;
     const bool yok = live && gy < a.ly;  // (uniform per wave)
     const uint32_t nzv = live ? min(8u, a.lz - z0) : 0u;
     const uint32_t slot = brick * kStreamWaves + (uint32_t)wid;
@@ -294,24 +283,10 @@ k_brick3_stream(const T* __restrict__ in, StreamArgs a, T ebx2_r, T r)
     bool wide = false;                  // a lane's four codewords of some row exceed 64 bits
     uint32_t bnext = kNoBrick;
     if (live) {
-      // phase 1: prequant, z-diff, x-diff inside the 8-wide tile (lrz_c.cuhip.inl:341-352 order)
-      T av[8][V];
-      {
-        T pprev[V];
+      // phase 1: prequant, z-diff, x-diff inside the 8-wide tile
+      T av[8][V], pprev[V];
 #pragma unroll
-        for (int z = 0; z < 8; z++) {
-#pragma unroll
-          for (int k = 0; k < V; k++) {
-            const T p = dround(q[z][k] * ebx2_r);
-            av[z][k] = z > 0 ? p - pprev[k] : p;
-            pprev[k] = p;
-          }
-          const T west = shr_in_tile<T, 1, 8 / V>(av[z][V - 1]);
-#pragma unroll
-          for (int k = V - 1; k > 0; k--) av[z][k] = av[z][k] - av[z][k - 1];
-          if (x0 % 8 != 0) av[z][0] = av[z][0] - west;
-        }
-      }
+      for (int z = 0; z < 8; z++) residual_zx(q[z], ebx2_r, z == 0, x0 % 8 == 0, pprev, av[z]);
       if (wid < kStreamWaves - 1)
 #pragma unroll
         for (int z = 0; z < 8; z++) lds_store4(xsT + ((size_t)z * 64 + lane) * V, av[z]);
@@ -320,8 +295,9 @@ k_brick3_stream(const T* __restrict__ in, StreamArgs a, T ebx2_r, T r)
       __syncthreads();  // (A) residuals exchanged, next brick known
       bnext = s_next[par ^ 1];
       par ^= 1;
+      const auto bn = ld.rows_of(bnext);  // (past the last brick: the loads read 0)
 #pragma unroll
-      for (int z = 0; z < 8; z++) ld.issue_row(bnext, 8 * wid + z, q[z]);
+      for (int z = 0; z < 8; z++) ld.issue_row(bn, (uint32_t)wid, (uint32_t)z, q[z]);
       if (!have_book) {  // first brick: the codebook (workgroup 0 raises the flag)
         if (threadIdx.x == 0) {
           for (uint32_t spin = 0;; spin++) {

@@ -263,7 +263,7 @@ int brick_configure(BrickLaunch& L, int elem_bytes, int device);
 // wave that completes the sample publishes it to the host (pub_dst, then *pub_flag = pub_epoch),
 // which builds the codebook while pass 1 goes on.  hist == nullptr: no sample, bricks in index order.
 // 3-D bricks count relaxed, and the completing wave accepts the sample once its bins sum to total
-// (brick_scan.hip finish_unit); linear bricks count with an agent-scope acq_rel and do not use total.
+// (brick_scan.hip finish_brick); linear bricks count with an agent-scope acq_rel and do not use total.
 // the sample histogram's bins lie a 64-B line apart: the sample bricks finish together (first
 // round of pass 1) and their atomics would otherwise queue on the one or two memory channels of
 // a dense 4 KB array (measured: pass 1 +60 us)
@@ -301,10 +301,10 @@ struct BrickPlanArgs {
   const uint16_t* bhist;  // per-brick histograms, stride brick_hist_stride(bklen)
   int bklen, bhs;
   const uint32_t* book;
-  uint32_t nbricks, nunits, nbx, nby, ly, lz;  // units of brick_units(): regions, slots, histograms
-  const uint32_t* brick_cnt;  // outliers per unit (pass 1)
-  uint32_t cap_per_brick;     // outlier slot capacity per unit
-  const uint64_t* slots;      // per-unit outlier slots
+  uint32_t nbricks, nbx, nby, ly, lz;
+  const uint32_t* brick_cnt;  // outliers per brick (pass 1)
+  uint32_t cap_per_brick;     // outlier slot capacity per brick
+  const uint64_t* slots;      // per-brick outlier slots
   const uint64_t* spill;
   const uint32_t* spill_cnt;
   uint32_t spill_cap;
@@ -322,15 +322,14 @@ struct BrickPlanArgs {
   size_t n = 0;          // 1-D: elements of the field
   uint32_t* ticket = nullptr;  // 9 words zeroed per call: the two-level last-block ticket
 };
-uint32_t brick_units(uint32_t nbricks);
 uint32_t brick_plan_blocks(uint32_t nbricks);
 int brick_hist_stride(int bklen);
 int launch_brick_plan(const BrickLaunch& L, const BrickPlanArgs& a, const void* psz_tpl, const void* phf_tpl,
                       hipStream_t st);
-// pass 2: brick-ordered codes -> Huffman cells at each brick's reserved region
+// pass 2: brick-ordered codes -> Huffman cells at each brick's reserved region (bricks last to first)
 int launch_brick_pack(const BrickLaunch& L, const BrickCodes& bc, const uint32_t* book, int bklen,
                       const BrickPlanArgs& plan, uint32_t* par_nbit, uint32_t* par_entry, uint32_t* bitstream,
-                      int reverse, unsigned int* overflow, hipStream_t st, const HostPub& pub = HostPub{});
+                      unsigned int* overflow, hipStream_t st, const HostPub& pub = HostPub{});
 struct BrickSingle {
   OutlierSink ol;              // one slot per (brick, y-step): cap_per_brick = the slot's cap
   uint32_t* book;              // device book (the stream kernel's workgroup 0 writes it)

@@ -68,6 +68,27 @@ __device__ __forceinline__ T shr_in_tile(T v)
     return __shfl_up(v, L);
 }
 
+// The 3-D predictor's z-then-x residual (lrz_c.cuhip.inl:341-352; the y-difference follows at the
+// call site) of a lane's four values of row z, two lanes per 8-wide tile: prequant p, a = p -
+// p(z - 1) unless z is the tile's first, then a -= a(x - 1) unless x is (tile_start: the lane
+// holds the tile's first four).  pprev carries p from row z - 1 to row z.  Bit-exactness rests on
+// this order of operations.
+template <typename T>
+__device__ __forceinline__ void residual_zx(const T (&raw)[4], T ebx2_r, bool first_z, bool tile_start, T (&pprev)[4],
+                                            T (&a)[4])
+{
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const T p = dround(raw[k] * ebx2_r);
+    a[k] = first_z ? p : p - pprev[k];
+    pprev[k] = p;
+  }
+  const T west = shr_in_tile<T, 1, 2>(a[3]);
+#pragma unroll
+  for (int k = 3; k > 0; k--) a[k] = a[k] - a[k - 1];
+  if (!tile_start) a[0] = a[0] - west;
+}
+
 __device__ __forceinline__ uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
 // ---- vector row I/O -------------------------------------------------------------------

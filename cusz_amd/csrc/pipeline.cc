@@ -63,7 +63,7 @@ int Pipeline::init(psz_dtype dt, psz_len l, void* st)
   uint32_t max_bricks = geom.nbricks;
   if (bl.g.ok) {
     CUSZ_AMD_HIP_CHECK((hipError_t)brick_configure(bl, elem_bytes, device));
-    brick_slot_cap = brick_unit_elems() / 10 + 16;
+    brick_slot_cap = bl.g.brick_elems / 10 + 16;
     max_bricks = std::max(max_bricks, bl.g.nbricks);
     CUSZ_AMD_HIP_CHECK(d_bhist.alloc((size_t)bl.g.nbricks * kMaxBklen));
     CUSZ_AMD_HIP_CHECK(d_ub.alloc(bl.g.nbricks));
@@ -162,7 +162,7 @@ int Pipeline::grow_spill(uint64_t need)
 int Pipeline::grow_slots(uint32_t need)
 {
   uint32_t& cap = bricks() ? brick_slot_cap : cap_per_brick;
-  const uint32_t lim = bricks() ? brick_unit_elems() : geom.brick_elems;
+  const uint32_t lim = bricks() ? bl.g.brick_elems : geom.brick_elems;
   const uint32_t want = (uint32_t)std::min<uint64_t>(lim, (uint64_t)need + need / 8 + 16);
   if (want <= cap) return 0;
   cap = want;

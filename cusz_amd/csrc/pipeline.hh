@@ -265,19 +265,14 @@ struct Pipeline {
   uint32_t* book_flag() { return &d_small.p->book_flag; }
   static constexpr uint32_t kStreamSlots = 8;  // outlier slots per brick in the single-pass mode (one per y-step)
 
-  // outlier slot per brick unit (brick_device.hh kUnitBricks bricks): 10 % of its elements + 16 at
-  // first; a compress whose bricks spill grows it to the largest brick's count (grow_slots)
+  // outlier slot per brick of the brick layout: 10 % of its elements + 16 at first; a compress
+  // whose bricks spill grows it to the largest brick's count (grow_slots)
   uint32_t brick_slot_cap = 0;
-  uint32_t brick_unit_elems() const
-  {
-    const uint32_t nu = brick_units(bl.g.nbricks), per = (bl.g.nbricks + nu - 1) / nu;
-    return bl.g.brick_elems * per;
-  }
-  // cells of every slot (reference-layout bricks and brick-layout units share d_slots)
+  // cells of every slot (the bricks of the reference layout and of the brick layout share d_slots)
   size_t slot_cells_total() const
   {
     size_t c = (size_t)geom.nbricks * cap_per_brick;
-    if (bl.g.ok) c = std::max(c, (size_t)brick_units(bl.g.nbricks) * brick_slot_cap);
+    if (bl.g.ok) c = std::max(c, (size_t)bl.g.nbricks * brick_slot_cap);
     return c;
   }
   int grow_events = 0;  // capacity growths (a compress that warned repeats only after one)

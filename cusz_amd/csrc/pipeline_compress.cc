@@ -378,17 +378,16 @@ int Pipeline::finish_brick(psz_header* h, uint8_t** out, size_t* outlen)
   fill_header_templates(lay, bklen, g.W, (int)g.nchunks, n, len, h, &ph);
 
   const uint32_t nblk = brick_plan_blocks(g.nbricks);
-  BrickPlanArgs pa{d_bhist, bklen, brick_hist_stride(bklen), d_book, g.nbricks, brick_units(g.nbricks), g.nbx, g.nby, bl.ly, bl.lz,
+  BrickPlanArgs pa{d_bhist, bklen, brick_hist_stride(bklen), d_book, g.nbricks, g.nbx, g.nby, bl.ly, bl.lz,
                    d_brick_cnt, brick_slot_cap, d_slots, d_spill, spill_cnt(), spill_cap, nblk, d_ub, d_bbase, d_brick_off,
                    d_plan, d_plan + nblk + 1, info(), d_archive, lay.phf_off, lay.bits_rel};
   pa.nd = g.ndim == 3 ? 3u : 1u, pa.nchunks = g.nchunks, pa.n = g.n;  // 1-D and 2-D: linear bricks
   pa.ticket = plan_ticket();
   CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_plan(bl, pa, h, &ph, stream));
   const PhfSections ps = phf_sections(lay);
-  // pass 2 walks bricks last-to-first (reuses pass 1's cache tail); its last workgroup publishes the summary
-  constexpr int kPackReverse = 1;
+  // pass 2's last workgroup publishes the summary
   CUSZ_AMD_HIP_CHECK((hipError_t)launch_brick_pack(bl, brick_codes(pend.zz, radius), d_book, bklen, pa, ps.par_nbit, ps.par_entry,
-                                                   ps.bits, kPackReverse, timeout(), stream, summary_pub()));
+                                                   ps.bits, timeout(), stream, summary_pub()));
   mark(kMarkEncode);
   if (int fs = book.build_if_armed(sampled)) return fs;
   mark(kMarkFinalize);

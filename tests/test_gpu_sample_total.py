@@ -1,6 +1,6 @@
 """The codebook sample inside pass 1 (3-D bricks) is accepted by value: the wave that completes it
 re-reads the sample histogram until its bins sum to the number of sample-brick elements inside
-the field, which brick_configure works out from the shape (brick_scan.hip finish_unit).
+the field, which brick_configure works out from the shape (brick_scan.hip finish_brick).
 
 What can go wrong, and what shows it:
   * a sample handed over early or incomplete, or a total that is too small: the host builds

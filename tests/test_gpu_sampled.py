@@ -34,6 +34,8 @@ CASES = [
     ((256, 16, 16), np.float32, 1e-2, False, 512, "noise"),    # u16 rows, long codes
     ((512, 16, 24), np.float32, 2e-3, False, 512, "noise"),    # ~10 bits/code: bricks outgrow the staging
     ((512, 128, 136), np.float32, 1e-4, False, 512, "smooth"),  # 1088 bricks: every 16th sampled
+    ((512, 16, 9), np.float64, 2e-5, False, 512, "smooth"),    # f64, partial bricks in z, 4 bricks
+    ((256, 13, 11), np.float32, 1e-3, True, 512, "smooth"),    # ZigZag, partial bricks in y and z
 ]
 
 
